@@ -17,11 +17,18 @@ Workload (N = number of GPUs, one process per GPU, Z-slab decomposition, weak sc
   Initial state: the default Params initial condition (u = 293.15 K, ice cap, glass walls and
   200 glass beads) built by libpft's host model code; t = 0, h = tau = 1 s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints one JSON line (contract in the task statement) with `roofline` (dominant stage
-kernel, HIP-event timed) and `cpu_baseline` (the CPU oracle port on a bounded sample, N=1 only).
+A plain run sets up, warms up, times the K attempted steps and has rank 0 print one JSON line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  The timed steps are
+attempted steps W+1 .. W+K from the initial condition in every run, so with the same arguments two
+runs compute the same state; --dump-outputs DIR writes it (dump_outputs below).
+
+--full adds everything else, each in a run of its own after the timed region: `roofline` (the
+dominant stage kernel, HIP-event timed in a separate pass), `cpu_baseline` (the CPU oracle port on
+a bounded sample, N=1 only), and with N > 1 the decomposition parity re-run (`parity`) and the
+strong-split sub-run (`config.strong`).  Without --full those keys are null.
 """
 import argparse
 import ctypes as C
@@ -32,6 +39,7 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
+DUMP_MAX_VALUES = 6 << 20   # --dump-outputs: doubles of the state written (48 MB), over all ranks
 PROBE_STEPS = 3    # attempted steps of the N > 1 setup's delivery check (bench.py main)
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -66,6 +74,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (module docstring): the stage-timing "
+                         "pass (roofline), the CPU baseline, and with N > 1 the parity re-run and the "
+                         "strong-split sub-run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they computed to DIR/x.npy (float64; a fixed "
+                         "seeded sample of a large state) and (t, h, steps, steps_total) to DIR/trajectory.npy")
     ap.add_argument("--prewarm-s", type=float, default=0.3,
                     help="before the W counted warm-up steps, run untimed attempted steps for about this "
                          "long so the GPU clock has left its idle level (0: off; DESIGN 5)")
@@ -74,7 +89,7 @@ def parse():
                     help="N>1 workload family (module docstring): cube/tall weak scaling; strong = the "
                          "--grid-nodes grid itself split N ways (BASELINE configs[3]: 400^3 4-way)")
     ap.add_argument("--no-strong", action="store_true",
-                    help="N>1: skip the strong-split sub-run (config.strong)")
+                    help="N>1 with --full: skip the strong-split sub-run (config.strong)")
     ap.add_argument("--literal-cube", action="store_true",
                     help="L1 = L2 = L3 = 0.06 m: G x G x G cells (SURVEY 8(d) secondary number)")
     ap.add_argument("--domain", default=None,
@@ -87,14 +102,14 @@ def parse():
                     help="1: per stage (default), 32 / 16: LDS-tiled kernel, 0: cache-based")
     ap.add_argument("--no-recompute", action="store_true",
                     help="materialise the reference's aux arrays between stages (72 vs 54 doubles/cell-step)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--host-ic", action="store_true",
                     help="initial condition on the host (default: on the device, bit-identical, f1)")
     ap.add_argument("--gate", type=int, default=0, choices=(0, 1),
                     help="gated steps on small single slabs (PFT_OPT_GATE, f4; default off: measured neutral)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
                     help="CPU sample: attempted steps (in batches of 2) until this much time has passed")
-    ap.add_argument("--no-timing", action="store_true", help="no HIP-event stage timing")
+    ap.add_argument("--no-timing", action="store_true", help="--full: no HIP-event stage timing")
     ap.add_argument("--host-boundary", action="store_true",
                     help="timed call is one RK_MPI_SA_solve-style call: x copied host->device at entry "
                          "and back at exit (PCIe-inclusive rate; never the headline value)")
@@ -113,10 +128,10 @@ def parse():
                     help="install a Service_Callback that reads t and h after every accepted step, as the "
                          "reference driver's RKService does with its default Params (intertrack.c:1072-1116)")
     ap.add_argument("--timing-steps", type=int, default=30,
-                    help="attempted steps of the separate, untimed pass that measures the stage kernels with "
+                    help="--full: attempted steps of the separate, untimed pass that measures the stage kernels with "
                          "HIP events (roofline); 0 = none")
     ap.add_argument("--no-parity", action="store_true",
-                    help="N > 1: skip the decomposition-invariance check (rank 0 re-runs the same attempted "
+                    help="N > 1 with --full: skip the decomposition-invariance check (rank 0 re-runs the same attempted "
                          "steps on one slab of its own GPU and compares every rank's state bit for bit)")
     ap.add_argument("--probe", type=int, default=0,
                     help="after the run, launch the 8-B/lane copy probe this many times "
@@ -195,7 +210,7 @@ def main():
                             gl_static=a.gl_static, kz=a.kz or None, tile=a.tile,
                             recompute=not a.no_recompute, device_ic=not a.host_ic)
 
-    probe_calls = []   # solve calls made by the setup's check (world > 1), replayed by the parity re-run
+    probe_calls = []   # solve calls made by the setup's check (world > 1), dropped with the pre-warm's
     if world > 1:
         # The first exchanges (the device IC's ghost planes) run inside the setup.  If the ipc transport
         # the run chose by itself fails there on any rank (mapping a neighbour's buffers across GPUs,
@@ -211,7 +226,7 @@ def main():
                 raise RuntimeError("the ghost planes after the setup exchange differ from the neighbours' planes")
             if not a.host_ic and a.transport in ("ipc", "ipc-ce"):
                 # the same after a few attempted steps: the split launches' exchanges (copy engines,
-                # boundary stream) -- the first solve call, replayed by the parity re-run like the rest
+                # boundary stream) -- the first solve call; the run goes back to the IC after the pre-warm
                 rc = sim.solve_ex(base["final_time"], PROBE_STEPS, P.PFT_SOLVE_KEEP_DEVICE)
                 probe_calls.append(PROBE_STEPS)
                 delivered = halo_delivered(L, sim, dist, world, rank)   # collective: every rank calls it
@@ -241,6 +256,7 @@ def main():
     else:
         sim = make_sim()
     init_s = time.time() - t0
+    x0 = sim.x.copy() if a.host_ic else None   # rewind(): the device IC is computed again instead
     cells_rank = n1 * n2 * sim.grid.n3
     cells_total = n1 * n2 * total_n3
     final_time = base["final_time"]
@@ -259,8 +275,8 @@ def main():
     # launch, profiles/r03b_clock_ramp_driver_config.txt), so a 20-step window right after start
     # measured 15 853-16 090 where the steady state is 17 592.  Untimed attempted steps of the same
     # solve run until --prewarm-s has passed (every rank takes the same decision: the max over
-    # ranks); they are solve calls like the warm-up, replayed by the N > 1 parity re-run.
-    calls = list(probe_calls)                  # the capped solve calls, in order (the parity re-run repeats them)
+    # ranks); the state they leave is dropped again below.
+    calls = list(probe_calls)                  # the capped solve calls, in order
     prewarm_steps = 0
     tp = time.perf_counter()
     while a.prewarm_s > 0 and prewarm_steps < 5000:
@@ -279,9 +295,16 @@ def main():
         if el_p >= a.prewarm_s:
             break
     prewarm_s = time.perf_counter() - tp
-    # warm-up: uploads x once (when not pre-warmed), builds the kernels' caches; W attempted steps
+    # The pre-warm ran for a time, not for a count of steps, so the state it leaves differs from run
+    # to run.  Back to the initial condition at t = 0 (a kernel with the device IC: the GPU stays
+    # busy): the timed steps are attempted steps W+1 .. W+K of the same trajectory in every run.
+    reuse = P.PFT_SOLVE_REUSE_DEVICE if calls else 0
+    if calls:
+        reuse = rewind(sim, base, x0)
+        calls = []                             # (from here on: what the N > 1 parity re-run repeats)
+    # warm-up: uploads x once (host IC), builds the kernels' caches; W attempted steps
     calls.append(max(1, a.warmup))
-    rc = sim.solve_ex(final_time, calls[-1], P.PFT_SOLVE_KEEP_DEVICE | (P.PFT_SOLVE_REUSE_DEVICE if len(calls) > 1 else 0))
+    rc = sim.solve_ex(final_time, calls[-1], P.PFT_SOLVE_KEEP_DEVICE | reuse)
     assert rc == 2, rc
     st0 = sim.system.steps_total
     barrier()
@@ -304,9 +327,14 @@ def main():
         el = float(tt.item())
     accepted = int(sim.system.steps)
     t_end = sim.t
+    if a.dump_outputs:
+        # what the timed call leaves its caller, before any later pass moves the state on
+        if not a.host_boundary:
+            sim.download()
+        dump_outputs(a.dump_outputs, sim, rank, world)
     # stage kernels timed in a separate pass after the timed region (HIP events on the slab's
     # compute stream, every other attempted step: each timed stage adds an event pair)
-    if not a.no_timing and a.timing_steps > 0:
+    if a.full and not a.no_timing and a.timing_steps > 0:
         L.pft_solver_set_option(P.PFT_OPT_TIMING, 2)
         rc = sim.solve_ex(final_time, a.timing_steps, P.PFT_SOLVE_KEEP_DEVICE | P.PFT_SOLVE_REUSE_DEVICE)
         assert rc == 2, rc
@@ -326,7 +354,7 @@ def main():
 
     # ---- roofline: dominant fused stage kernel, HIP events on the slab's compute stream -----
     roof = None
-    if not a.no_timing and stats.stage_n[1] > 0:
+    if a.full and not a.no_timing and stats.stage_n[1] > 0:
         per = {}
         nl = {s: 1 for s in range(1, 6)}
         for s in range(1, 6):
@@ -435,16 +463,16 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1 only): the oracle port, bounded sample -----------------
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         cpu = cpu_baseline(sim, base, a)
     out["cpu_baseline"] = cpu
-    mine = slab_digest(sim) if (world > 1 and not a.no_parity) else None
+    mine = slab_digest(sim) if (world > 1 and a.full and not a.no_parity) else None
     sim.close()
     if comm is not None:
         L.pft_comm_set_current(None)
         L.pft_comm_destroy(comm)
 
-    # ---- N > 1: decomposition invariance, checked on every run --------------------
+    # ---- N > 1: decomposition invariance, checked on every --full run -------------
     ok = True
     if mine is not None:
         ranks = [None] * world
@@ -475,7 +503,7 @@ def main():
 #     GPUs, ipc when ranks share one) or ipc-ce and any rank fails -- an exchange that never
 #     arrives (the bounded waits end it), a device error, a parity mismatch -- every rank is
 #     started again over RCCL.  The JSON line records every attempt ("launch").
-# With N > 1 a second set of ranks then times the reference's 400^3 grid split N ways (BASELINE
+# With N > 1 and --full a second set of ranks then times the reference's 400^3 grid split N ways (BASELINE
 # configs[3] at N = 4: 200 x 200 x 100 per rank) with its own parity re-run: config.strong.
 PARITY_EXIT = 3
 
@@ -612,7 +640,7 @@ def supervise(a):
             print(f"bench supervisor (rank {rank}): the run over '{tr}' failed on a rank; every rank starts again "
                   f"over RCCL in fresh processes", file=sys.stderr)
     strong = None
-    if success and world > 1 and not a.no_strong and a.shape != "strong" and not a.self_exchange:
+    if success and world > 1 and a.full and not a.no_strong and a.shape != "strong" and not a.self_exchange:
         # BASELINE configs[3] (at N = 4): the 400^3 grid split N ways, over the transport the main run used
         tr = (out or {}).get("config", {}).get("transport") or "auto" if rank == 0 else "auto"
         trl = [tr]
@@ -665,6 +693,37 @@ def dryrun_worker(a):
                           "config": {"transport": tr, "shape": a.shape, "ranks": names}}))
     dist.destroy_process_group()
     return 0
+
+
+def rewind(sim, base, x0):
+    """put the solver back at the initial condition, t = 0, h = tau, no steps counted; returns the
+    flag the next solve call needs (device IC: it is computed again into the resident state, as in
+    Simulation's setup, collective with N > 1; host IC x0: the next call uploads it)"""
+    s = sim.system
+    s.t, s.h, s.steps, s.steps_total = 0.0, base["tau"], 0, 0
+    if x0 is not None:
+        sim.x[:] = x0
+        return 0
+    rc = sim.lib.pft_solver_ic_default_device(1)
+    if rc:
+        raise RuntimeError(f"pft_solver_ic_default_device failed ({rc}): {sim.lib.pft_hip_last_error()}")
+    return P.PFT_SOLVE_REUSE_DEVICE
+
+
+def dump_outputs(path, sim, rank, world):
+    """--dump-outputs: this rank's interior state x[field][k][j][i] after the timed steps as float64
+    in DIR/x.npy (N > 1: x_rank<r>.npy), flattened; a state of more than DUMP_MAX_VALUES / N values
+    is sampled at fixed seeded positions (sorted, the same in every run).  Rank 0 also writes
+    trajectory.npy: t, h, accepted and attempted steps since the initial condition."""
+    os.makedirs(path, exist_ok=True)
+    x = sim.interior().reshape(-1)
+    cap = DUMP_MAX_VALUES // world
+    if x.size > cap:
+        x = x[np.unique(np.random.default_rng(1000 + rank).integers(0, x.size, cap))]
+    np.save(os.path.join(path, "x.npy" if world == 1 else f"x_rank{rank}.npy"), x.astype(np.float64))
+    if rank == 0:
+        s = sim.system
+        np.save(os.path.join(path, "trajectory.npy"), np.array([s.t, s.h, s.steps, s.steps_total], dtype=np.float64))
 
 
 def halo_delivered(L, sim, dist, world, rank):

@@ -6,7 +6,7 @@ mkdir -p $OUT
 while read -r label args; do
   [ -z "$label" ] && continue
   for pair in 1 0; do
-    PFT_PAIR=$pair timeout -k 10 300 python bench.py --no-cpu $args > $OUT/${label}_p$pair.json 2>>$OUT/err.log
+    PFT_PAIR=$pair timeout -k 10 300 python bench.py --full --no-cpu $args > $OUT/${label}_p$pair.json 2>>$OUT/err.log
     rc=$?; [ $rc -ne 0 ] && { echo "$label failed: $rc"; exit $rc; }
     python3 -c "import json;d=json.load(open('$OUT/${label}_p$pair.json'));print('$label p$pair'.ljust(16), d['value'], d['ms_per_step'], (d['roofline'] or {}).get('stages_ms'))"
   done

@@ -8,7 +8,7 @@ mkdir -p $OUT
 for rep in $(seq ${REPS:-1}); do
   while read -r label lib envs; do
     [ -z "$label" ] && continue
-    env $envs PFT_LIB=$PWD/porousfreezethaw_amd/$lib/libpft.so timeout -k 10 300 python bench.py --steps ${STEPS:-100} --warmup 5 --no-cpu $ARGS > $OUT/${label}_r${rep}.json 2>>$OUT/err.log
+    env $envs PFT_LIB=$PWD/porousfreezethaw_amd/$lib/libpft.so timeout -k 10 300 python bench.py --steps ${STEPS:-100} --warmup 5 --full --no-cpu $ARGS > $OUT/${label}_r${rep}.json 2>>$OUT/err.log
     rc=$?; [ $rc -ne 0 ] && { echo "$label failed: $rc"; exit $rc; }
     python3 -c "import json;d=json.load(open('$OUT/${label}_r${rep}.json'));print('$label'.ljust(14), d['value'], d['ms_per_step'], (d['roofline'] or {}).get('stages_ms'))"
   done <<< "$CASES"

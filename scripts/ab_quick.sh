@@ -13,7 +13,7 @@ for lib in ${LIBS:-lib lib_alt}; do
 done
 for rep in $(seq ${REPS:-2}); do
   for lib in ${LIBS:-lib lib_alt}; do
-    PFT_LIB=$PWD/porousfreezethaw_amd/$lib/libpft.so timeout -k 10 300 python bench.py --steps ${STEPS:-200} --warmup 10 --no-cpu $ARGS > $O/${lib}_r${rep}.json 2>>$O/err.log || { echo "$lib bench failed"; exit 1; }
+    PFT_LIB=$PWD/porousfreezethaw_amd/$lib/libpft.so timeout -k 10 300 python bench.py --steps ${STEPS:-200} --warmup 10 --full --no-cpu $ARGS > $O/${lib}_r${rep}.json 2>>$O/err.log || { echo "$lib bench failed"; exit 1; }
     python3 -c "import json;d=json.load(open('$O/${lib}_r${rep}.json'));print('$lib'.ljust(10), d['value'], d['ms_per_step'], (d['roofline'] or {}).get('stages_ms'))"
   done
 done

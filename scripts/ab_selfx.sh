@@ -9,7 +9,7 @@ for dom in "400 0.06,0.06,0.015 n8" "318 0.06,0.06,0.03 n4" "252 0.06,0.06,0.06 
   set -- $dom
   for pair in ${PAIRS:-1 0}; do
     for tr in none ipc rccl; do
-      args="--steps 100 --no-cpu --grid-nodes $1 --domain $2"
+      args="--steps 100 --full --no-cpu --grid-nodes $1 --domain $2"
       [ $tr != none ] && args="$args --self-exchange --transport $tr"
       PFT_PAIR=$pair timeout -k 10 300 python bench.py $args > $OUT/$3_p${pair}_$tr.json 2>>$OUT/err.log
       rc=$?; [ $rc -ne 0 ] && { echo "$3 $tr failed: $rc"; exit $rc; }

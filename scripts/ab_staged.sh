@@ -8,7 +8,7 @@ O=gpurun_out/stg
 mkdir -p $O
 for r in 1 2; do
   for st in 0 1; do
-    PFT_IPC_STAGED=$st timeout -k 10 300 python bench.py --steps 100 --no-cpu --grid-nodes 400 --domain 0.06,0.06,0.015 --self-exchange --transport ipc > $O/n8_staged${st}_$r.json 2>> $O/err.log || exit 1
+    PFT_IPC_STAGED=$st timeout -k 10 300 python bench.py --steps 100 --full --no-cpu --grid-nodes 400 --domain 0.06,0.06,0.015 --self-exchange --transport ipc > $O/n8_staged${st}_$r.json 2>> $O/err.log || exit 1
     python3 -c "import json;d=json.load(open('$O/n8_staged${st}_$r.json'));print('staged=$st', d['value'], d['ms_per_step'], d['roofline']['stages_ms'])"
   done
 done

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 O=gpurun_out/abx
 mkdir -p $O
 run() { local tag=$1; shift   # (an environment assignment before `run` reaches bench.py)
-  timeout -k 10 300 python bench.py --no-cpu --steps ${STEPS:-100} "$@" > $O/one.json 2>> $O/err.log || { echo "[$tag] failed $?"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu --steps ${STEPS:-100} "$@" > $O/one.json 2>> $O/err.log || { echo "[$tag] failed $?"; exit 1; }
   python3 -c "import json,sys; d=json.load(open('$O/one.json')); d['tag']='$tag'; print(json.dumps(d))" >> $O/runs.jsonl
   python3 -c "import json; d=json.load(open('$O/one.json')); print('$tag', d['value'], d['ms_per_step'])"
 }

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/fb
 mkdir -p $O
-timeout -k 10 400 python bench.py > $O/default.json 2> $O/default.err || exit 1
+timeout -k 10 400 python bench.py --full > $O/default.json 2> $O/default.err || exit 1
 for r in 1 2 3; do
   timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu > $O/driver_$r.json 2>> $O/err.log || exit 1
 done

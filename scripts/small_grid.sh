@@ -9,7 +9,7 @@ mkdir -p $O
 for g in 100 200; do
   st=$([ $g = 100 ] && echo 2000 || echo 400)
   for pair in 0 2; do
-    PFT_PAIR=$pair timeout -k 10 300 python bench.py --grid-nodes $g --steps $st --warmup 50 --no-cpu > $O/g${g}_p$pair.json 2>> $O/err.log || exit 1
+    PFT_PAIR=$pair timeout -k 10 300 python bench.py --grid-nodes $g --steps $st --warmup 50 --full --no-cpu > $O/g${g}_p$pair.json 2>> $O/err.log || exit 1
     python3 -c "import json;d=json.load(open('$O/g${g}_p$pair.json'));print('g$g pair=$pair', d['value'], d['ms_per_step'], d['roofline']['stages_ms'])"
   done
 done

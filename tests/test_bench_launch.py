@@ -40,9 +40,9 @@ def _run(args, fail=None, torchrun=0, timeout=180):
 
 
 def test_plain_launch_spawns_n_ranks():
-    """a plain `bench.py --gpus 3`: three child ranks with distinct processes and ranks 0..2, rank 0's
-    line forwarded on stdout with the launch record; then the strong-split set of ranks"""
-    r, out = _run(["--gpus", "3", "--steps", "2", "--warmup", "1"])
+    """a plain `bench.py --gpus 3 --full`: three child ranks with distinct processes and ranks 0..2,
+    rank 0's line forwarded on stdout with the launch record; then (--full) the strong-split set of ranks"""
+    r, out = _run(["--gpus", "3", "--steps", "2", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert out["dryrun"] and out["n_gpus"] == 3
     ranks = out["config"]["ranks"]
@@ -53,6 +53,15 @@ def test_plain_launch_spawns_n_ranks():
     assert out["launch"]["attempts"] == [{"transport": "auto", "exit_codes": [0, 0, 0], "ok": True}]
     assert out["config"]["strong"]["scaling"] == "strong"
     assert r.stdout.count("\n") == 1                    # exactly one line on stdout
+
+
+def test_plain_launch_without_full_has_no_strong_split():
+    """without --full the launcher starts the one set of ranks the headline figure needs"""
+    r, out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert out["launch"]["attempts"] == [{"transport": "auto", "exit_codes": [0, 0], "ok": True}]
+    assert "strong" not in out["config"]
+    assert r.stderr.count("rank exit codes [") == 1
 
 
 def test_plain_launch_propagates_a_rank_failure():
