@@ -39,6 +39,10 @@ typedef struct {
 	double cp_g, cp_i, cp_w;
 	double lam_g, lam_i, lam_w;
 	double top_temp1, top_temp2, phase_switch_time;
+	/* filled by the slab, never by the model (pft_model_get_consts leaves it zero): the refined
+	   reciprocal the division by alpha starts from, brought to (1, 2] (div_alpha,
+	   pft_kernels.hip), computed on the device whenever alpha changes */
+	double ralpha;
 } pft_consts;
 
 typedef struct pft_slab pft_slab;   /* opaque: device buffers + streams of one slab */
@@ -146,6 +150,12 @@ int pft_slab_rhs(pft_slab * s, int in_buf, int out_buf, double t);
 
 /* refresh the model constants / per-variable error multipliers of an existing slab */
 int pft_slab_set_consts(pft_slab * s, const pft_consts * c);
+/* test entry: the kernels' division by alpha (div_alpha: the reciprocal's refinement computed once
+   per alpha) against the plain IEEE division on the device, for n_hashed hashed bit patterns
+   (splitmix64 of 0 .. n_hashed - 1) and the n_list patterns of list; *mismatches: results whose
+   bits differ (0 required) */
+int pft_div_alpha_check(double alpha, unsigned long long n_hashed, const unsigned long long * list,
+                        unsigned long long n_list, unsigned long long * mismatches);
 int pft_slab_set_eps_mult(pft_slab * s, const double * em3);
 
 /* u_noise field (PrecalculateData, equation.c:450-456), n3*n1*n2 doubles [k][j][i]; NULL clears */

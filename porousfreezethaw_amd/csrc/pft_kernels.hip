@@ -78,6 +78,75 @@ __device__ __forceinline__ double sshape(const pft_consts& c, double x)
   return x * x * (c.e23 - c.e32 * x);
 }
 
+// n / c.alpha, bit for bit the compiler's IEEE division, which on gfx950 is
+//   d0 = div_scale(alpha; alpha, n)   d1 = div_scale(n; alpha, n)   (powers of two keeping 1/d0 and
+//   r = rcp(d0), two Newton steps: e = fma(-d0, r, 1), r = fma(r, e, r)       the quotient normal)
+//   q = d1 * r;  e = fma(-d0, q, d1);  div_fixup(div_fmas(e, r, q), alpha, n)
+// The second line depends on alpha alone, a launch constant, and costs a transcendental and four
+// FMAs at every cell.  Here r comes from c.ralpha: the same refinement, computed once on the device
+// when the constants are set (div_alpha_consts_kernel) and stored times the power of two that
+// brings it to (1, 2].  d0 is alpha times a power of two, and the refinement scales with its
+// operand exactly (every intermediate is normal), so r(d0) = ralpha 2^-frexp_exp(d0); where
+// div_scale leaves alpha as it is, that is the very r the compiler's sequence has.  No branch and
+// no range check: scaling and special cases stay with div_scale and div_fixup as before.
+// -DPFT_DIV_ALPHA_HOIST=0: the plain `/` (A/B).
+#ifndef PFT_DIV_ALPHA_HOIST
+#define PFT_DIV_ALPHA_HOIST 1
+#endif
+__device__ __forceinline__ double div_alpha(double n, const pft_consts& c)
+{
+#if PFT_DIV_ALPHA_HOIST && defined(__HIP_DEVICE_COMPILE__)
+  bool sd, sn;
+  const double d0 = __builtin_amdgcn_div_scale(n, c.alpha, false, &sd);
+  const double d1 = __builtin_amdgcn_div_scale(n, c.alpha, true, &sn);
+  const double r = __builtin_ldexp(c.ralpha, -__builtin_amdgcn_frexp_exp(d0));
+  const double q = d1 * r;
+  const double e = __builtin_fma(-d0, q, d1);
+  return __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(e, r, q, sn), c.alpha, n);
+#else
+  return n / c.alpha;
+#endif
+}
+
+// c.ralpha for one alpha, by one lane.  Where alpha and its reciprocal are normal with room to
+// spare, the refinement runs on alpha itself -- the compiler's operands for a numerator that makes
+// div_scale leave alpha alone -- and the result is moved to (1, 2] (exact: a power of two).  Any
+// other alpha (subnormal, huge) is first brought to [0.5, 1).
+__global__ void div_alpha_consts_kernel(double alpha, double* out)
+{
+  const int ex = __builtin_amdgcn_frexp_exp(alpha);
+  const bool plain = ex > -900 && ex < 900;
+  const double d = plain ? alpha : __builtin_ldexp(alpha, -ex);
+  double r = __builtin_amdgcn_rcp(d);
+  double e = __builtin_fma(-d, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  e = __builtin_fma(-d, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  out[0] = plain ? __builtin_ldexp(r, ex) : r;
+}
+
+// test entry (pft_div_alpha_check): div_alpha against `/` on nh hashed bit patterns (splitmix64 of
+// the index: every exponent, both signs) and on the nl patterns of list; counts the mismatches
+__global__ __launch_bounds__(256) void div_alpha_check_kernel(pft_consts c, unsigned long long nh,
+                                                              const unsigned long long* list, unsigned long long nl,
+                                                              unsigned long long* bad)
+{
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nh + nl) return;
+  unsigned long long b;
+  if (i < nh) {
+    b = i + 0x9E3779B97F4A7C15ULL;
+    b = (b ^ (b >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    b = (b ^ (b >> 27)) * 0x94D049BB133111EBULL;
+    b ^= b >> 31;
+  } else {
+    b = list[i - nh];
+  }
+  const double n = __longlong_as_double((long long)b);
+  const double got = div_alpha(n, c), ref = n / c.alpha;
+  if (__double_as_longlong(got) != __double_as_longlong(ref)) atomicAdd(bad, 1ULL);
+}
+
 // K (du, dp) at one cell; dgl is identically 0 (equation.c:731,874)
 template <int MODE>
 __device__ __forceinline__ void rhs_cell(const pft_consts& c, const Col& u, const Col& p, const Col& g,
@@ -123,7 +192,7 @@ __device__ __forceinline__ void rhs_cell(const pft_consts& c, const Col& u, cons
       dpdt += c.xi2a * pc * (1.0 - pc) * (pc - 0.5) -
               c.sam * sshape(c, pc) * sshape(c, 1.0 - pc) * fmax(pc * (1.0 - pc), 0.0) * (un - c.u_star);
     }
-    dpdt /= c.alpha;
+    dpdt = div_alpha(dpdt, c);
     dpdt *= wi;
     dp = dpdt;
     if (MODE == 0 || MODE == 1) du = (flux / rho + c.L * dpdt) / cp;
@@ -192,7 +261,7 @@ __device__ __forceinline__ void rhs_cell_f(const pft_consts& c, const Col& u, co
       dpdt += c.xi2a * pc * (1.0 - pc) * (pc - 0.5) -
               c.sam * sshape(c, pc) * sshape(c, 1.0 - pc) * fmax(pc * (1.0 - pc), 0.0) * (un - c.u_star);
     }
-    dpdt /= c.alpha;
+    dpdt = div_alpha(dpdt, c);
     dpdt *= wi;
     dp = dpdt;
     if (MODE == 0 || MODE == 1) du = (flux / rho + c.L * dpdt) / cp;
@@ -2197,7 +2266,9 @@ struct SlabPeer {
 
 struct pft_slab {
   pft_slab_desc d;
-  pft_consts c;
+  pft_consts c;          // (ralpha: slab_div_consts)
+  double da_alpha, da_r; // the alpha it was computed for, and the value
+  int da_valid;
   long fs;
   int plane;
   double* buf[PFT_BUF_COUNT];
@@ -2491,6 +2562,29 @@ int pft_hip_device_sync(void)
 
 static long pair_geometry(int n1, int n2, int* tx_out, int* ty_out);
 
+// c.ralpha for s->c.alpha (div_alpha): one lane on the device, when alpha changes
+static int slab_div_consts(pft_slab* s)
+{
+  if (!s->da_valid || memcmp(&s->da_alpha, &s->c.alpha, sizeof(double)) != 0) {
+    double* d = nullptr;
+    double h = 0.0;
+    hipError_t e = hipMalloc((void**)&d, sizeof(h));
+    if (e == hipSuccess) {
+      div_alpha_consts_kernel<<<1, 1, 0, s->stream>>>(s->c.alpha, d);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (d) (void)hipFree(d);
+    if (e != hipSuccess) return fail(e, "div_alpha constants");
+    s->da_alpha = s->c.alpha;
+    s->da_r = h;
+    s->da_valid = 1;
+  }
+  s->c.ralpha = s->da_r;
+  return 0;
+}
+
 int pft_slab_create(pft_slab** out, const pft_slab_desc* d, const pft_consts* c)
 {
   *out = nullptr;
@@ -2577,6 +2671,10 @@ int pft_slab_create(pft_slab** out, const pft_slab_desc* d, const pft_consts* c)
   if (e != hipSuccess) {
     pft_slab_destroy(s);
     return fail(e, "slab buffers/streams");
+  }
+  if (int rc = slab_div_consts(s)) {
+    pft_slab_destroy(s);
+    return rc;
   }
   *out = s;
   return 0;
@@ -3196,6 +3294,41 @@ int pft_slab_set_recompute(pft_slab* s, int on)
 int pft_slab_set_consts(pft_slab* s, const pft_consts* c)
 {
   s->c = *c;
+  return slab_div_consts(s);
+}
+
+int pft_div_alpha_check(double alpha, unsigned long long n_hashed, const unsigned long long* list,
+                        unsigned long long n_list, unsigned long long* mismatches)
+{
+  pft_consts c;
+  memset(&c, 0, sizeof(c));
+  c.alpha = alpha;
+  double* dc = nullptr;
+  unsigned long long *dl = nullptr, *db = nullptr;
+  *mismatches = ~0ULL;
+  if (n_hashed + n_list > (1ULL << 31) || (n_list && !list)) return -2;
+  hipError_t e = hipMalloc((void**)&dc, sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&db, 8);
+  if (e == hipSuccess && n_list) e = hipMalloc((void**)&dl, 8 * (size_t)n_list);
+  if (e == hipSuccess && n_list) e = hipMemcpy(dl, list, 8 * (size_t)n_list, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(db, 0, 8);
+  if (e == hipSuccess) {
+    div_alpha_consts_kernel<<<1, 1>>>(alpha, dc);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(&c.ralpha, dc, sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) {
+    const unsigned long long n = n_hashed + n_list;
+    if (n) {
+      div_alpha_check_kernel<<<(unsigned)((n + 255) / 256), 256>>>(c, n_hashed, dl, n_list, db);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpy(mismatches, db, 8, hipMemcpyDeviceToHost);
+  if (dc) (void)hipFree(dc);
+  if (dl) (void)hipFree(dl);
+  if (db) (void)hipFree(db);
+  if (e != hipSuccess) return fail(e, "pft_div_alpha_check");
   return 0;
 }
 
