@@ -1157,10 +1157,16 @@ __global__ __launch_bounds__(PFT_FBLOCK) __attribute__((amdgpu_waves_per_eu(STAG
 //
 // Positions beyond the 512 threads (round 6, the 40 x 20 tile: 22 x 24 = 528 positions).  The
 // last ring row (py = ty + 3) is only read, as the y neighbours of stage A's last row; its
-// positions past thread 511 (at most PFT_PAIR_NEX, all in that row) are loaded by lanes 0..15 of
-// the last wave as LDS DMA (global_load_lds_dwordx4: no registers -- the kernel has none to spare
-// at 256 VGPRs) into the staging array lX one plane ahead, and at the next iteration's start the
-// same lanes combine them into stage A's input and store it into lA with the other positions'.
+// positions past thread 511 (at most PFT_PAIR_NEX, all in that row) are loaded by the last lanes
+// of the last wave, whose own positions are load-only (ring rows 0 and ty + 3): such a lane never
+// reads plane mm's operand set (rc: stage B's input and lO belong to the other rows) and is done
+// with plane mm + 1's (rn) after the top of the step, so of the three rotating PairRaw sets two
+// hold nothing it needs.  It loads the extra position's operands into rn with ordinary loads, one
+// step ahead, and a step later -- the set is rc by then -- combines them into stage A's input and
+// stores it into lA: no register the allocation does not already hold, no staging in LDS.  (Round 6
+// staged them by LDS DMA, global_load_lds_dwordx4 through hand-ordered asm, on the premise that
+// the kernel has no register to spare at 256 VGPRs; that cost pair 4+5 about 4%: DESIGN.md
+// section 8.00000.)
 // The taller tile evaluates stage B on 400 positions instead of 380 with the same wave-phases per
 // plane, n2 = 200 / 400 is cut into 10 / 20 tile rows with no idle row (19-row tiles: 11 / 22, the
 // last one half empty), and 400^3 runs its 50 tiles x 5 z-chunks in one round of 250 workgroups
@@ -1333,29 +1339,6 @@ struct PairLds {
   __device__ static __forceinline__ double cell(const double* L, int p, int s) { return L[2 * p + s]; }
 };
 
-// One 16-byte LDS DMA per active lane (global_load_lds_dwordx4): lane l of the wave writes the 16
-// bytes at g into LDS byte address lds + 16 l.  Inline asm rather than
-// __builtin_amdgcn_global_load_lds: hipcc treats the builtin's pending LDS write as a reason to wait
-// for vmcnt(0) at the next barrier and at the next use of an ordinary load -- it would drain the
-// look-ahead loads and the output stores every plane (MI355X guide, "Pipelining across barriers").
-// Invisible to the compiler, the DMA is ordered by hand: its reader waits with a counted vmcnt
-// (pair_x_wait), and the "memory" clobber keeps the reads of the previous plane's staging before it
-// and the look-ahead loads after it.  M0 is not used by any other instruction of these kernels.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void lds_dma16(unsigned lds, const void* base, unsigned off)
-{
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(off), "s"(base) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-// the staging of the previous plane's DMA has landed: every vector-memory operation but the N
-// youngest is done (loads, stores and LDS DMA count together in issue order, MI355X guide)
-template <int N>
-__device__ __forceinline__ void pair_x_wait()
-{
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // the RHS of one cell pair (du, dp of both cells): centre zc, z neighbours zm / zp, x/y
 // neighbours from the LDS field planes L[q] around slot p (even / odd halves, row pitch LWP); the
 // x-face between the pair's cells is evaluated once and the z-face below is carried in fz
@@ -1409,8 +1392,10 @@ __device__ __forceinline__ void pair_rhs(const pft_consts& c, const double* L0, 
 // the load-only rows 0 and ty + 3 -- the last of them beyond the threads (pair_geometry_ok: at most
 // PFT_PAIR_NEX, all in row ty + 3).  With 22-pair rows (40 x 20 tile) stage B's 20 rows end at
 // thread 439, so the last wave (448 .. 511) holds ring rows only and skips stage B: its SIMD runs 3
-// wave-phases a plane where the others run 4, and the extra positions' staging and DMA ride in that
-// slack instead of delaying the barrier.  (Stage-B positions compacted to threads 0 .. 399, ring
+// wave-phases a plane where the others run 4, and the extra positions' combine and LDS stores ride
+// in that slack instead of delaying the barrier.  The threads that take an extra position, the
+// last NPOS - 512 of the order, lie in the load-only rows (NPOS - 512 <= tx/2 + 2, since rows
+// 0 .. ty + 2 fit the threads: pair_geometry_ok), which is what frees their registers.  (Stage-B positions compacted to threads 0 .. 399, ring
 // columns after them, did the same for pair 2+3 but cost pair 4+5 9%: its rows no longer one run;
 // profiles/r06_ab_pair_tile.txt.)  Row-major from row 0 for tiles without extra positions.
 __device__ __forceinline__ void pair_pos(int v, int bw, int ty, int& px, int& py)
@@ -1466,15 +1451,10 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
   // (without OPL a 1 x 1 placeholder: its accesses below sit in a branch that is constant-false
   // there, which -Warray-bounds flags per instantiation; an if constexpr would drop the placeholder
   // and shift the LDS layout of every other kernel)
-  // lO, then the extra positions' operands of the next plane (x u, p, gl; K1 u, p; K3 u, p), staged
-  // by LDS DMA (lX), in one array: the DMA's wave-uniform base lX - 16 (first loader lane) bytes
-  // must not fall below the LDS (without OPL a 64-slot pad takes lO's place)
-  constexpr int LXOFF = OPL ? 6 * PFT_PAIR_OPN : 64;
-  __shared__ __attribute__((aligned(16))) dbl2 lOX[LXOFF + 7 * PFT_PAIR_NEX];
-  dbl2(*const lO)[PFT_PAIR_OPN] = reinterpret_cast<dbl2(*)[PFT_PAIR_OPN]>(lOX);
-  dbl2* const lX = lOX + LXOFF;
+  __shared__ __attribute__((aligned(16))) dbl2 lO[OPL ? 6 : 1][OPL ? PFT_PAIR_OPN : 1];
   // the extra positions' acting-pair offsets, set once (the tile's corner x0, y0 is not kept live
-  // across the loop for them: pair 4+5 has no register or SGPR to spare)
+  // across the loop for them: pair 4+5 has no register or SGPR to spare, and recomputing the corner
+  // takes the tile's index through xcd_remap, where this is one LDS read)
   __shared__ unsigned lXa[PFT_PAIR_NEX];
 
   const int TX = a.tx, TY = a.ty, WP2 = TX / 2 + 2, NPOS = WP2 * (TY + 4);
@@ -1520,11 +1500,11 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
   const int ob = (py - 2) * (TX / 2) + px - 1;                // this stage-B position's slot in lO
   // positions beyond the threads (NPOS > PFT_PBLOCK: pair_geometry_ok puts them all in the last
   // ring row ty + 3, the tail of pair_pos's order): the last NPOS - PFT_PBLOCK threads (lanes
-  // 64 - NEX .. 63 of the last wave, themselves load-only positions) load one each too, by LDS DMA
-  // into lX one plane ahead like their own look-ahead, and store its stage-A input into lA with
-  // their own.  Everything about it is recomputed where used from the thread index and the phase's
-  // kernel arguments (mostly scalar): the kernel holds no register for it across the loop (pair
-  // 4+5 is at 256 VGPRs).
+  // 64 - NEX .. 63 of the last wave, themselves load-only positions) load one each too, one plane
+  // ahead like their own look-ahead, into the operand set that is dead for them (xload in step()),
+  // and store its stage-A input into lA a step later.  Everything else about it is recomputed
+  // where used from the thread index and the phase's kernel arguments (mostly scalar): the kernel
+  // holds no further register for it across the loop (pair 4+5 is at 256 VGPRs).
   auto nex = [&](const PairArgs& A) { return (A.tx / 2 + 2) * (A.ty + 4) - PFT_PBLOCK; };
   // the loaders are lanes 64 - NEX .. 63 of the last wave; inside the z-loop they are found from
   // the wave's index (one SGPR) and the lane index (mbcnt, recomputed): keeping threadIdx.x live
@@ -1542,36 +1522,13 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
   auto apo_x = [&](const PairArgs& A) { return lXa[lane() - (64 - nex(A))]; };
   auto pos_x = [&](const PairArgs& A) { return PFT_PAIR_PADP + (A.ty + 3) * LWP + px_x(A); };
   auto pboe = [&](const PairArgs& A, int m) -> unsigned { return ((unsigned)(m + 2) * (unsigned)A.plane + apo_x(A)) * 8u; };
-  // the DMA of plane m's operands of the extra position into lX (this lane: slot xs of each array)
-  auto dma = [&](const PairArgs& A, int m) {
-    const unsigned bo = pboe(A, m);
-    const unsigned l0 = (unsigned)(size_t)((__attribute__((address_space(3))) dbl2*)lX) -
-                        16u * (unsigned)(64 - nex(A));       // lane 64 - NEX -> slot 0
-    const unsigned fb = (unsigned)A.fs * 8u;                  // a field's bytes (pft_slab_pair_ok: 3 fb < 4 GiB)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) lds_dma16(l0 + (0 + q) * 16 * PFT_PAIR_NEX, A.x, bo + q * fb);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) lds_dma16(l0 + (3 + q) * 16 * PFT_PAIR_NEX, A.k1, bo + q * fb);
-    if (SA == 4) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) lds_dma16(l0 + (5 + q) * 16 * PFT_PAIR_NEX, A.k3, bo + q * fb);
-    }
-  };
-  // stage A's input of the extra position from the staging (after pair_x_wait), field by field,
-  // into the ring slot `slot`
-  auto xstore = [&](const PairArgs& A, int slot) {
-    const int xs = lane() - (64 - nex(A));                   // this loader's slot in lX (0 .. NEX - 1)
+  // plane m's operands of the extra position into the set r (call under is_x only)
+  auto xload = [&](const PairArgs& A, int m, PairRaw& r) { pair_load<SA>(A, pboe(A, m), r); };
+  // stage A's input of the extra position from its operands r into the ring slot `slot`
+  auto xstore = [&](const PairArgs& A, int slot, const PairRaw& r) {
     const int pe = pos_x(A);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      PairRaw t;
-      t.x[q] = lX[(0 + q) * PFT_PAIR_NEX + xs];
-      if (q < 2) {
-        t.k1[q] = lX[(3 + q) * PFT_PAIR_NEX + xs];
-        if (SA == 4) t.k3[q] = lX[(5 + q) * PFT_PAIR_NEX + xs];
-      }
-      LD::st(lA[slot][q], pe, pair_in_A<SA, GLX>(A, q, t));
-    }
+    for (int q = 0; q < 3; ++q) LD::st(lA[slot][q], pe, pair_in_A<SA, GLX>(A, q, r));
   };
 
   const int kb = bshort ? chunk * (a.n3 - 2) : a.k_begin + chunk * a.kz;
@@ -1642,7 +1599,8 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
     for (int s = 0; s < 2; ++s) fzA[s] = face_of(c, iam[1][s], iam[2][s], iam[0][s], ia0[1][s], ia0[2][s], ia0[0][s], FLUX);
     if (is_x(a)) {
-      // the extra position: planes mA0 - 1 and mA0 as the others' (loaded here), mA0 + 1 by DMA
+      // the extra position: planes mA0 - 1 and mA0 as the others' (loaded here), mA0 + 1 into
+      // R[0], the first step's rc, which a load-only lane is done with (ia0 above was its last use)
       PairRaw t;
       if (mA0 > mfirst) {
         pair_load<SA>(a, pboe(a, mA0 - 1), t);
@@ -1656,7 +1614,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         LD::st(lA[0][q], pos_x(a), v);
         if (mA0 == mfirst) LD::st(lA[2][q], pos_x(a), v);
       }
-      if (mA0 + 1 <= mlast) dma(a, mA0 + 1);                // consumed in the first step's stage-B slot
+      if (mA0 + 1 <= mlast) xload(a, mA0 + 1, R[0]);        // consumed at the top of the first step
     }
     if (mA0 + 1 <= mlast) pair_load<SA>(a, pbo(mA0 + 1), R[1]);
     KA[2][0] = KA[2][1] = zero2;
@@ -1683,6 +1641,23 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
           const dbl2 v = pair_in_A<SA, GLX>(A0, q, rn);
           LD::st(lA[sAp][q], posA, v);
           if (ZREG) IA[sAp][q] = v;
+        }
+      }
+      // The extra positions (last wave only, the test on wid is wave-uniform).  Plane mm + 1's
+      // operands are in rc, loaded a step ago (the prologue's into R[0]): their stage-A input goes
+      // into lA here, beside the own position's, ahead of the barrier.  Then plane mm + 2's operands
+      // into rn, which a load-only lane is done with: its next readers, as rc, are the next step's
+      // stage-B input and lO store, on rows it does not hold.  The loads go out ahead of the own
+      // position's look-ahead: loads count in issue order, so the wait for that look-ahead at the
+      // top of the next step covers these too, and the other waves, which skip the branch, wait for
+      // theirs exactly as without it.  (Behind the look-ahead, the compiler's count for it would
+      // have to assume these in flight after it in every wave, and drain to zero.)  Every load has
+      // its consumer: mm + 2 <= mlast <= ke + 1 leaves mm < ke, so the next step runs.  The last
+      // wave holds no stage-B position (pair_pos), so its SIMD has the wave-phase to spare.
+      if constexpr (LWP == 22) {
+        if (is_x(A0)) {
+          if (mm + 1 <= mlast) xstore(A0, sAp, rc);
+          if (mm + 2 <= mlast) xload(A0, mm + 2, rn);
         }
       }
       if (mm + 2 <= mlast) pair_load<SA>(A0, pbo(mm + 2), rnn);          // look-ahead
@@ -1827,23 +1802,6 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         }
       }
     }
-    {
-      PFT_PAIR_BIND(A3, C3);
-      (void)C3;
-      if (is_x(A3)) {
-        // the extra positions, in the last wave's stage-B slot (it holds no stage-B position, its
-        // SIMD has a wave-phase to spare: pair_pos), after stage B, where few registers are live:
-        // plane mm + 1's operands from the staging (its DMA went out an iteration ago; the wait for
-        // everything this wave issued is only the last wave's), stage A's input into lA, then plane
-        // mm + 2's DMA -- not in the chunk's last step, so that no DMA is left outstanding when the
-        // workgroup ends
-        if (mm + 1 <= mlast) {
-          pair_x_wait<0>();
-          xstore(A3, (PH + 1) % 3);
-        }
-        if (mm + 2 <= mlast && mm < ke) dma(A3, mm + 2);
-      }
-    }
     if (mm == ke) return false;
     __syncthreads();
     return true;
@@ -1879,11 +1837,15 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         if (red[q] > bm) bm = red[q];
         bnf |= rnf[q];
       }
+      // (the norm's arguments re-read here like the z-loop's: loaded with the prologue's, the
+      // compiler carried these twelve SGPRs across the whole kernel in spill lanes)
+      PFT_PAIR_BIND(AE, CE);
+      (void)CE;
       // gl's error-norm term: the same constant at every cell (its K's are literal zeros)
-      if (a.evgl > bm) bm = a.evgl;
-      bnf |= !isfinite(a.evgl);
-      if (a.part) eps_store_part(a.part, bm, bnf);
-      else eps_arrive(bm, bnf, a.shards, a.eps_bits, a.nonfinite, a.pub, a.pub_count);
+      if (AE.evgl > bm) bm = AE.evgl;
+      bnf |= !isfinite(AE.evgl);
+      if (AE.part) eps_store_part(AE.part, bm, bnf);
+      else eps_arrive(bm, bnf, AE.shards, AE.eps_bits, AE.nonfinite, AE.pub, AE.pub_count);
     }
   }
   if (bw) {
@@ -3804,7 +3766,8 @@ static int pair_lwp(int tx) { return tx <= 20 ? 12 : 22; }
 static bool pair_geometry_ok(int tx, int ty)
 {
   const int lwp = pair_lwp(tx);
-  // positions: one per thread, and up to PFT_PAIR_NEX more in the last ring row (LDS DMA)
+  // positions: one per thread, and up to PFT_PAIR_NEX more in the last ring row (loaded by
+  // the last lanes of the last wave beside their own: merson_pair)
   return tx >= 2 && tx % 2 == 0 && ty >= 1 &&
          (tx / 2 + 2) * (ty + 4) <= (lwp == 22 ? PFT_PBLOCK + PFT_PAIR_NEX : PFT_PBLOCK) &&
          (tx / 2 + 2) * (ty + 3) <= PFT_PBLOCK && tx / 2 + 2 <= 22 &&
@@ -3815,7 +3778,7 @@ static bool pair_geometry_ok(int tx, int ty)
 // automatic tile: the fewest workgroups per plane (a workgroup-plane costs about the same whatever
 // the tile's edge tiles hold), of those the one with the fewest idle tile cells, then the wider.
 // n1 = 200 / 400: 40 x 20 cells (5 x 10 / 10 x 20 tiles, 484 of 512 threads evaluate stage A and
-// 400 stage B, 16 positions of the last ring row DMA-staged; 40 x 19 before round 6); n1 = 100: 20 x 34 cells (5 x 3 tiles, 98% of their cells in the plane, against 18
+// 400 stage B, 16 positions of the last ring row loaded by load-only lanes; 40 x 19 before round 6); n1 = 100: 20 x 34 cells (5 x 3 tiles, 98% of their cells in the plane, against 18
 // 34 x 19 tiles with the 22-pair pitch alone).  Returns the tiles per plane, 0 when no tile fits
 // (n1 odd).
 static long pair_geometry(int n1, int n2, int* tx_out, int* ty_out)
@@ -4053,8 +4016,8 @@ int pft_slab_pair_ok(const pft_slab* s)
   // plane would need the neighbour's u_noise there (not exchanged: one launch per stage then)
   const bool nb = s->d.has_below || s->d.has_above;
   if (nb && (s->d.n3 < 2 || s->noise)) return 0;
-  // (merson_pair addresses a field with 32-bit byte offsets, and the extra positions' LDS DMA the
-  // three fields of a buffer from one base: 3 fields < 4 GiB, 178 M cells per slab)
+  // (merson_pair addresses a field with 32-bit byte offsets; the limit is the one the round-6 LDS
+  // DMA set, the three fields of a buffer from one base: 3 fields < 4 GiB, 178 M cells per slab)
   return s->pair_on && slab_kind(s) == KFUSED &&
          3.0 * (double)s->fs * 8.0 < 4294967296.0 && s->pair_ntile > 0;
 }
