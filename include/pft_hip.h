@@ -100,6 +100,21 @@ int pft_slab_set_tile(pft_slab * s, int wx);
 /* the kernel flavour (0 cache, 2 fused recompute; 1 is retired) and tile (wx cell pairs x ty
    rows; 0 x 0 for the cache kernel) that stage 1..5 launches on this slab */
 int pft_slab_tile_geometry(const pft_slab * s, int stage, int * wx, int * ty);
+/* the grid of the last launch that produced stage 1..5 on this slab (a pair launch counts as its
+   second stage, 3 or 5; of a split stage the launch issued last): its workgroups (without the
+   extra one of a speculative stage 1 that reduces the error norm), the planes each marches and
+   the tiles per plane.  Returns 0 for a launch over a range of planes (a whole slab, or a split
+   stage's interior), 1 when that last launch was a split stage's boundary launch, whose "kz" is the
+   distance between its two groups of boundary planes and whose chunks are those two groups; -2
+   before the first such launch. */
+int pft_slab_launch_geometry(const pft_slab * s, int stage, int * nwg, int * kz, int * ntile);
+/* the linear (chunk, tile) index that block b of a launch of n workgroups works on: the kernels'
+   own xcd_remap, for a test that needs the cell of a given block */
+int pft_xcd_remap(int b, int n);
+/* how the workgroups of the last error-norm launch (stage 5 or pair 4+5) handed in their maxima:
+   1 = deferred partials, reduced by the next stage-1 launch; 0 = the sharded arrival atomics;
+   -2 before the first such launch */
+int pft_slab_eps_route(const pft_slab * s);
 /* 1 (default): the tiled kernels rebuild every stage input from x and the K's inside the
    stencil (no aux arrays: 39 instead of 72 doubles of traffic per cell-step, bit-identical);
    0: the reference's aux arrays are materialised between stages (cache kernel) */

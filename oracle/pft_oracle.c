@@ -205,7 +205,7 @@ void pft_or_rhs(const pft_or_grid * g, const double * param, int calc_mode, doub
 
 /* ---------------------------------------------------------------------------------------- */
 /* RK-Merson, RK_MPI_SAsolver_hybrid2.c:215-770 over the intertrack chunk table
-   (intertrack.c:2144-2157: one chunk per interior row, chunk_eps_mult = 1) */
+   (intertrack.c:2144-2157: one chunk per interior row; chunk_eps_mult = 1 unless given) */
 
 #define CMD_UPDATE 4
 #define CMD_FINISHED 8
@@ -238,28 +238,56 @@ static void rhs_stage(const pft_or_grid * g, const double * P, int cm, double t,
 }
 
 static double eps_max(const rows_t * R, const double * K1, const double * K3, const double * K4,
-                      const double * K5)
+                      const double * K5, const double * cm, const unsigned char * skip,
+                      pft_or_step_rec * rec)
 {
-	/* hybrid2.c:507-524 (OpenMP 3.1 max reduction); NaN never wins (e>eps is false) */
+	/* hybrid2.c:507-524 (OpenMP 3.1 max reduction) over the chunk table in its own order (q, k, j),
+	   e = chunk_eps_mult[c] * |...| (:521); NaN never wins (e>eps is false).  skip: cells left out
+	   of the maximum (a kernel that loses them, restated).  The value is a maximum, so it does not
+	   depend on the OpenMP schedule; the arg-max is found afterwards by a serial scan: the first
+	   cell in index order that holds the value. */
+	const int n1 = R->g->n1, n2 = R->g->n2, n3 = R->g->n3;
 	double eps = 0.0;
 	int q, k, j, i;
 	for(q=0;q<NV;q++) {
 		#pragma omp parallel for private(j, i) reduction(max:eps) schedule(static)
-		for(k=0;k<R->g->n3;k++) for(j=0;j<R->g->n2;j++) {
-			long b = q*R->d.S + (BT+k)*R->d.row + (long)(BT+j)*R->d.N1 + BT;
-			for(i=0;i<R->g->n1;i++) {
-				double e = 1.0 * fabs(0.2*K1[b+i] - 0.9*K3[b+i] + 0.8*K4[b+i] - 0.1*K5[b+i]);
+		for(k=0;k<n3;k++) for(j=0;j<n2;j++) {
+			const long b = q*R->d.S + (BT+k)*R->d.row + (long)(BT+j)*R->d.N1 + BT;
+			const long c = ((long)q*n3 + k)*n2 + j;
+			const double mult = cm ? cm[c] : 1.0;
+			const unsigned char * sk = skip ? skip + c*n1 : NULL;
+			for(i=0;i<n1;i++) {
+				double e = mult * fabs(0.2*K1[b+i] - 0.9*K3[b+i] + 0.8*K4[b+i] - 0.1*K5[b+i]);
+				if(sk && sk[i]) continue;
 				if(e > eps) eps = e;
 			}
 		}
 	}
+	if(rec) {
+		rec->eps = eps; rec->q = rec->k = rec->j = rec->i = -1;
+		if(eps > 0.0)
+			for(q=0;q<NV && rec->q<0;q++) for(k=0;k<n3 && rec->q<0;k++) for(j=0;j<n2 && rec->q<0;j++) {
+				const long b = q*R->d.S + (BT+k)*R->d.row + (long)(BT+j)*R->d.N1 + BT;
+				const long c = ((long)q*n3 + k)*n2 + j;
+				const double mult = cm ? cm[c] : 1.0;
+				for(i=0;i<n1;i++) {
+					if(skip && skip[c*n1 + i]) continue;
+					if(mult * fabs(0.2*K1[b+i] - 0.9*K3[b+i] + 0.8*K4[b+i] - 0.1*K5[b+i]) == eps) {
+						rec->q = q; rec->k = k; rec->j = j; rec->i = i;
+						break;
+					}
+				}
+			}
+	}
 	return eps;
 }
 
-int pft_or_solve(const pft_or_grid * g, const double * P, int cm,
-                 double final_time, double * tp, double * hp, double h_min, double delta,
-                 int delta_local, double * x, long * steps, long * steps_total,
-                 long max_steps_total, pft_or_exchange_fn ex, pft_or_allreduce_fn ar, void * user)
+int pft_or_solve_ex(const pft_or_grid * g, const double * P, int cm,
+                    double final_time, double * tp, double * hp, double h_min, double delta,
+                    int delta_local, double * x, long * steps, long * steps_total,
+                    long max_steps_total, pft_or_exchange_fn ex, pft_or_allreduce_fn ar, void * user,
+                    const double * chunk_mult, const unsigned char * skip,
+                    pft_or_step_rec * rec, long rec_cap, long * rec_n)
 {
 	rows_t R; long n;
 	double *K1, *K3, *K4, *K5, *aux, *K2;
@@ -268,6 +296,7 @@ int pft_or_solve(const pft_or_grid * g, const double * P, int cm,
 	long attempted = 0;
 
 	R.g = g; R.d = dims_of(g); n = NV*R.d.S;
+	if(rec_n) *rec_n = 0;
 	if(delta <= 0) return -2;
 	K1 = (double*)calloc(n, sizeof(double)); K3 = (double*)calloc(n, sizeof(double));
 	K4 = (double*)calloc(n, sizeof(double)); K5 = (double*)calloc(n, sizeof(double));
@@ -291,7 +320,9 @@ int pft_or_solve(const pft_or_grid * g, const double * P, int cm,
 		rhs_stage(g, P, cm, t+h, aux, K5, ex, user);                    /* :453 */
 
 		(*steps_total)++; attempted++;                                  /* :460 */
-		eps = eps_max(&R, K1, K3, K4, K5);
+		eps = eps_max(&R, K1, K3, K4, K5, chunk_mult, skip,
+		              (rec && attempted <= rec_cap) ? &rec[attempted-1] : NULL);
+		if(rec && rec_n && attempted <= rec_cap) *rec_n = attempted;
 		if(ar) ar(&eps, user);                                          /* :572 */
 		if(delta_local) eps *= fabs(h3);                               /* :578 */
 		new_h = ((eps>0.0) ? pow((delta/eps),0.2)*0.8 : 2.0) * h;      /* :580 */
@@ -313,6 +344,16 @@ int pft_or_solve(const pft_or_grid * g, const double * P, int cm,
 	*tp = t;
 	free(K1); free(K3); free(K4); free(K5); free(aux);
 	return ret;
+}
+
+int pft_or_solve(const pft_or_grid * g, const double * P, int cm,
+                 double final_time, double * tp, double * hp, double h_min, double delta,
+                 int delta_local, double * x, long * steps, long * steps_total,
+                 long max_steps_total, pft_or_exchange_fn ex, pft_or_allreduce_fn ar, void * user)
+{
+	/* multipliers 1, nothing skipped, no record */
+	return pft_or_solve_ex(g, P, cm, final_time, tp, hp, h_min, delta, delta_local, x, steps, steps_total,
+	                       max_steps_total, ex, ar, user, NULL, NULL, NULL, 0, NULL);
 }
 
 /* ---------------------------------------------------------------------------------------- */

@@ -67,6 +67,26 @@ int pft_or_solve(const pft_or_grid * g, const double * param, int calc_mode,
                  long max_steps_total, pft_or_exchange_fn exchange, pft_or_allreduce_fn allreduce,
                  void * user);
 
+/* one attempted step of pft_or_solve_ex: the error norm before the DELTA_LOCAL scaling
+   (hybrid2.c:507-524, before :578) and the cell that holds it -- variable q, interior plane k, row
+   j, column i; the first such cell in index order, all -1 when the norm is 0 */
+typedef struct { double eps; int q, k, j, i; } pft_or_step_rec;
+
+/* pft_or_solve with the inputs of the step-size decision exposed:
+     chunk_mult  chunk_eps_mult of the intertrack chunk table in its own order (q, k, j;
+                 3*n3*n2 values), e = chunk_mult[c] * fabs(...) (hybrid2.c:521); NULL: all 1
+     skip        [3][n3][n2][n1] bytes, non-zero: that cell is left out of the maximum (a kernel
+                 that loses a cell's contribution, restated on the CPU); NULL: none
+     rec         records of the first rec_cap attempted steps, *rec_n of them written; NULL: none
+   The maximum's value does not depend on the OpenMP schedule, and the arg-max is found by a serial
+   scan.  pft_or_solve is this with NULL, NULL, NULL. */
+int pft_or_solve_ex(const pft_or_grid * g, const double * param, int calc_mode,
+                    double final_time, double * t, double * h, double h_min, double delta,
+                    int delta_local, double * x, long * steps, long * steps_total,
+                    long max_steps_total, pft_or_exchange_fn exchange, pft_or_allreduce_fn allreduce,
+                    void * user, const double * chunk_mult, const unsigned char * skip,
+                    pft_or_step_rec * rec, long rec_cap, long * rec_n);
+
 /* default Params initial condition (Params:9-21 evaluated as the reference evaluator does) +
    PrecalculateData glass beads (equation.c:459-530); beads = nbeads x 3 unit-cube centres */
 void pft_or_ic_default(const pft_or_grid * g, const double * param, const double * beads,

@@ -32,6 +32,12 @@
  *        >= 0, a Service_Callback (hybrid2.c:670-705) that logs every call (steps, t, h) to
  *        <outdir>/cb.txt and returns 1 on its break_at-th call (0 = never); traj.txt rows gain
  *        RK_MPI_SA_check_NAN(); <outdir>/wall<i>.txt holds the wall seconds of call i
+ *
+ * Options, read before the command (none given: every invocation above runs as it always has); they
+ * act on solve and solvex:
+ *   --delta local|global     RK_MPI_S_SOLUTION.delta_mode (hybrid2.c:578; default DELTA_GLOBAL)
+ *   --mult <u>,<p>,<gl>      chunk_eps_mult (hybrid2.c:521) of every chunk of that variable
+ *   --mult-odd-planes <v>    chunk_eps_mult 1 on the even global planes k and v on the odd ones
  */
 
 #include "common.h"
@@ -284,6 +290,10 @@ static RK_RightHandSide (*pick_meta(void))()
 	return mf_middle;
 }
 
+/* options (see the head of this file) */
+static int opt_delta_local = 0;
+static double opt_mult[VAR_COUNT] = { 1.0, 1.0, 1.0 }, opt_mult_odd = 1.0;
+
 int main(int argc, char ** argv)
 {
 	int q;
@@ -295,7 +305,22 @@ int main(int argc, char ** argv)
 	MPI_Comm_size(MPI_COMM_WORLD, &MPIprocs);
 	MPIrankmap = (int*)malloc(sizeof(int)*MPIprocs);
 	for(q=0;q<MPIprocs;q++) MPIrankmap[q] = q;
-	if(argc < 4) { fprintf(stderr, "usage: pft_ref setup|rhs|solve <Params> <outdir> ...\n"); return 1; }
+	while(argc > 2 && !strncmp(argv[1], "--", 2)) {
+		if(!strcmp(argv[1], "--delta")) {
+			if(!strcmp(argv[2], "local")) opt_delta_local = 1;
+			else if(!strcmp(argv[2], "global")) opt_delta_local = 0;
+			else { fprintf(stderr, "--delta global|local\n"); return 1; }
+		} else if(!strcmp(argv[1], "--mult")) {
+			char tail;
+			if(sscanf(argv[2], "%lf,%lf,%lf%c", &opt_mult[0], &opt_mult[1], &opt_mult[2], &tail) != 3) { fprintf(stderr, "--mult u,p,gl\n"); return 1; }
+		} else if(!strcmp(argv[1], "--mult-odd-planes")) {
+			char * end;
+			opt_mult_odd = strtod(argv[2], &end);
+			if(end == argv[2] || *end) { fprintf(stderr, "--mult-odd-planes <number>\n"); return 1; }
+		} else { fprintf(stderr, "unknown option %s\n", argv[1]); return 1; }
+		argv += 2; argc -= 2;
+	}
+	if(argc < 4) { fprintf(stderr, "usage: pft_ref [options] setup|rhs|solve|solvex <Params> <outdir> ...\n"); return 1; }
 
 	load_params(argv[2]);
 	decompose();
@@ -340,12 +365,12 @@ int main(int argc, char ** argv)
 		/* chunk table, intertrack.c:2144-2157 */
 		for(q=0;q<VAR_COUNT;q++) for(k=0;k<n3;k++) for(j=0;j<n2;j++) {
 			cs[c] = q*subgridSIZE + (k+bcond_thickness)*rowsize + (j+bcond_thickness)*N1 + bcond_thickness;
-			cz[c] = n1; cm[c] = 1.0; c++;
+			cz[c] = n1; cm[c] = opt_mult[q] * (((first_row+k) & 1) ? opt_mult_odd : 1.0); c++;
 		}
 		{
 			RK_MEM_DIST md = { n_chunks, cs, cz, cm };
 			RK_MPI_S_SOLUTION sys = { &md, strtod(argv[5], NULL), solution, NULL, strtod(argv[6], NULL),
-			                          tau_min, delta_, DELTA_GLOBAL, NULL, NULL, 0L, 0L };
+			                          tau_min, delta_, opt_delta_local ? DELTA_LOCAL : DELTA_GLOBAL, NULL, NULL, 0L, 0L };
 			sys.meta_f = pick_meta();
 			if(RK_MPI_SA_init(VAR_COUNT*subgridSIZE, MPI_COMM_WORLD, 0)) MPI_Abort(MPI_COMM_WORLD, 8);
 			if(RK_MPI_SA_check_mem(&md)) MPI_Abort(MPI_COMM_WORLD, 9);

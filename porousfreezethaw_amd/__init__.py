@@ -217,11 +217,22 @@ class Simulation:
     (:1803-1827, :2144-2157), the model (equation.c contract), and the solver
     (RK_MPI_SA_init :2192, check_mem :2208, PrecalculateData :2218), then solves with
     RK_MPI_SA_solve (:2283) or the device-resident pft_solve_ex.
+
+    delta_mode: DELTA_GLOBAL (the driver's, intertrack.c:2165) or DELTA_LOCAL (the error norm times
+    |h/3| before it is compared with delta, hybrid2.c:578).  chunk_mult: the chunk table's
+    chunk_eps_mult (hybrid2.c:521) -- None (1, as the driver leaves them), three per-variable
+    values (u, p, gl), or one value per chunk in the table's order (q, k, j; 3*n3*n2 of this
+    slab).  It is written into self.chunk_mult after PrecalculateData, whose argument is that
+    array (the reference's leaves it alone, equation.c:533, and so does libpft's: checked here),
+    and before RK_MPI_SA_check_mem, so the solver sees it from its first call.
     """
 
     def __init__(self, n1, n2, total_n3, L, calc_mode, params, nprocs=1, rank=0, beads=None,
                  initial=None, tau=1.0, tau_min=0.0, delta=1e-3, t0=0.0, gl_static=False, kz=None,
-                 init_solver=True, tile=None, recompute=True, icond=None, device_ic=False):
+                 init_solver=True, tile=None, recompute=True, icond=None, device_ic=False,
+                 delta_mode=DELTA_GLOBAL, chunk_mult=None):
+        if delta_mode not in (DELTA_LOCAL, DELTA_GLOBAL):
+            raise ValueError(f"delta_mode must be DELTA_LOCAL or DELTA_GLOBAL, not {delta_mode!r}")
         if device_ic and (initial is not None or not init_solver):
             # checked before any host IC work: the device IC overwrites X/XN and the host copy
             raise ValueError("device_ic computes the IC (the default Params', or icond=) on an initialised "
@@ -278,7 +289,7 @@ class Simulation:
                                                 ("mf_top" if rank == nprocs - 1 else "mf_middle"))
         self.meta_addr = C.cast(getattr(L_, meta), C.c_void_p).value
         self.system = RK_MPI_S_SOLUTION(C.pointer(self.mem), t0, _dp(self.x), self.meta_addr, tau,
-                                        tau_min, delta, DELTA_GLOBAL, None, None, 0, 0)
+                                        tau_min, delta, delta_mode, None, None, 0, 0)
         L_.pft_solver_set_option(PFT_OPT_GL_STATIC, 1 if gl_static else 0)
         L_.pft_solver_set_option(PFT_OPT_KZ, kz or 0)   # 0: automatic
         L_.pft_solver_set_option(PFT_OPT_TILE, 1 if tile is None else tile)   # 1: per stage
@@ -295,6 +306,15 @@ class Simulation:
             L_.pft_model_set_solution(None)
         if L_.PrecalculateData(_dp(self.chunk_mult)):
             raise RuntimeError("PrecalculateData failed")
+        if not np.all(self.chunk_mult == 1.0):
+            raise RuntimeError("PrecalculateData changed chunk_eps_mult")
+        if chunk_mult is not None:
+            cm = np.asarray(chunk_mult, dtype=np.float64)
+            if cm.size == 3:
+                cm = np.repeat(cm.reshape(3), g.n3 * g.n2)
+            if cm.size != nch:
+                raise ValueError(f"chunk_mult: 3 or {nch} values (q, k, j), not {cm.size}")
+            self.chunk_mult[:] = cm.reshape(-1)     # in place: self.mem points at this array
         if init_solver:
             rc = L_.RK_MPI_SA_init(3 * self.S, MPI_COMM_WORLD, 0)
             if rc:

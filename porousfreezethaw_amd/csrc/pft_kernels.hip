@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void eps_reduce_kernel(const unsigned long lon
 }
 
 
-__device__ __forceinline__ int xcd_remap(int b, int n)
+__host__ __device__ __forceinline__ int xcd_remap(int b, int n)
 {
   // bijective: the blocks the dispatcher deals to one XCD (b % 8 equal) get consecutive ids
   const int q = n >> 3, r = n & 7, x = b & 7, l = b >> 3;
@@ -2312,6 +2312,9 @@ struct pft_slab {
   double fgeo_eff;
   long kz_key[16];                   // z-chunk cost model: key (occupancy, tiles, planes) -> kz
   int kz_val[16];
+  int launch_nwg[6], launch_kz[6], launch_ntile[6];   // the last launch that ended stage 1..5 (pft_slab_launch_geometry)
+  int launch_bnd[6];                 // ... and whether it was the boundary launch of a split stage
+  int launch_part;                   // ... and whether the last error-norm launch stored deferred partials
   long pub_next;                     // slots used so far
   int pub_armed;                     // the last stage-5 launch publishes into slot pub_slot
   int pub_slot;
@@ -2969,6 +2972,23 @@ int pft_slab_tile_geometry(const pft_slab* s, int stage, int* wx, int* ty)
   return kind;
 }
 
+int pft_slab_launch_geometry(const pft_slab* s, int stage, int* nwg, int* kz, int* ntile)
+{
+  if (stage < 1 || stage > 5 || !s->launch_nwg[stage]) return -2;
+  *nwg = s->launch_nwg[stage];
+  *kz = s->launch_kz[stage];
+  *ntile = s->launch_ntile[stage];
+  return s->launch_bnd[stage] ? 1 : 0;
+}
+
+int pft_xcd_remap(int b, int n) { return xcd_remap(b, n); }
+
+int pft_slab_eps_route(const pft_slab* s)
+{
+  if (!s->launch_nwg[5]) return -2;
+  return s->launch_part ? 1 : 0;
+}
+
 int pft_slab_stage_fields(const pft_slab* s, int stage)
 {
   // fields of a stage's output buffer that the stage writes (stage 6: the speculative stage 1):
@@ -3147,6 +3167,13 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
     s->pub_slot = j;
   }
   dim3 g((unsigned)(a.nbw + a.nint));
+  if (stage >= 1) {
+    s->launch_nwg[stage] = a.nbw + a.nint;
+    s->launch_kz[stage] = a.kz;
+    s->launch_ntile[stage] = a.ntile;
+    s->launch_bnd[stage] = bnd ? 1 : 0;
+    if (stage == 5) s->launch_part = a.part != nullptr;
+  }
   bool extra = false;
   // a stage launch's interior fills the chip: its boundary runs beside it only in bnd_mode 1 (slower:
   // the two launches' workgroups are dealt interleaved and the interior ends late).  In the boundary
@@ -3913,6 +3940,10 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
     }
   }
   const long nwg = (long)a.nbw + (long)a.nint;   // the launch's workgroups
+  s->launch_nwg[first + 1] = (int)nwg;
+  s->launch_kz[first + 1] = a.kz;
+  s->launch_ntile[first + 1] = a.ntile;
+  s->launch_bnd[first + 1] = bnd ? 1 : 0;
   a.T_topA = t_a < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
   a.T_topB = t_b < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
   // exactly the solver's h/3.0, h/6.0 and h/8.0 (and run_stage's stage-input coefficients)
@@ -3955,6 +3986,7 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
     s->pub_armed = 1;
     s->pub_slot = s->defer_slot;
   }
+  if (first == 4) s->launch_part = a.part != nullptr;
   const dim3 g((unsigned)nwg);
   hipStream_t st = s->stream;
   // bnd_mode 1, 2: the boundary launch beside the interior one.  On a 400 x 400 plane the interior

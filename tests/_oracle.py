@@ -30,6 +30,11 @@ class Grid(C.Structure):
                 ("L1", C.c_double), ("L2", C.c_double), ("L3", C.c_double)]
 
 
+class StepRec(C.Structure):
+    """pft_or_step_rec: an attempted step's error norm (before the DELTA_LOCAL scaling) and arg-max"""
+    _fields_ = [("eps", C.c_double), ("q", C.c_int), ("k", C.c_int), ("j", C.c_int), ("i", C.c_int)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_void_p)
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_void_p)
 
@@ -50,6 +55,9 @@ def lib():
                                    C.c_double, C.c_int, dp, C.POINTER(C.c_long), C.POINTER(C.c_long),
                                    C.c_long, EXCHANGE_FN, ALLREDUCE_FN, C.c_void_p]
         L.pft_or_solve.restype = C.c_int
+        L.pft_or_solve_ex.argtypes = L.pft_or_solve.argtypes + [dp, C.POINTER(C.c_ubyte), C.POINTER(StepRec),
+                                                              C.c_long, C.POINTER(C.c_long)]
+        L.pft_or_solve_ex.restype = C.c_int
         L.pft_or_ic_default.argtypes = [C.POINTER(Grid), dp, dp, C.c_int, dp]
         L.pft_or_set_noise.argtypes = [dp]
         L.pft_or_set_noise.restype = None
@@ -144,6 +152,48 @@ def solve(info, P, mode, state, t0, h0, times, max_steps_total=0, noise=None):
             res.append((t.value, h.value, steps.value, total.value, rc, unpad(g, x)))
     finally:
         lib().pft_or_set_noise(None)
+    return res
+
+
+def chunk_mult_array(info, chunk_mult):
+    """None, three per-variable values or a full table -> chunk_eps_mult in the intertrack table's
+    order (q, k, j), 3*n3*n2 values (None stays None)"""
+    if chunk_mult is None:
+        return None
+    n2, n3 = info["n2"], info["n3"]
+    cm = np.asarray(chunk_mult, dtype=np.float64)
+    if cm.size == 3:
+        cm = np.repeat(cm.reshape(3), n3 * n2)
+    assert cm.size == 3 * n3 * n2
+    return np.ascontiguousarray(cm.reshape(-1))
+
+
+def solve_ex(info, P, mode, state, t0, h0, times, max_steps_total=0, delta_local=False, chunk_mult=None,
+             skip=None, nrec=16):
+    """pft_or_solve_ex on one slab: as solve(), with DELTA_LOCAL, chunk multipliers (None, three
+    per-variable values or the full (q, k, j) table) and a skip mask [3][n3][n2][n1] of cells left
+    out of the error maximum.  Returns [(t, h, steps, total, rc, state, recs)], recs the
+    (eps, (q, k, j, i)) of that call's first nrec attempted steps."""
+    g = make_grid(info)
+    x = pad(g, state)
+    t, h = C.c_double(t0), C.c_double(h0)
+    steps, total = C.c_long(0), C.c_long(0)
+    cm = chunk_mult_array(info, chunk_mult)
+    sk = None
+    if skip is not None:
+        sk = np.ascontiguousarray(skip, dtype=np.uint8)
+        assert sk.shape == (3, info["n3"], info["n2"], info["n1"])
+    res = []
+    for T in times:
+        recs, nr = (StepRec * nrec)(), C.c_long(0)
+        rc = lib().pft_or_solve_ex(C.byref(g), ptr(P), mode, T, C.byref(t), C.byref(h), info["tau_min"],
+                                   info["delta"], 1 if delta_local else 0, ptr(x), C.byref(steps),
+                                   C.byref(total), max_steps_total, EXCHANGE_FN(), ALLREDUCE_FN(), None,
+                                   None if cm is None else ptr(cm),
+                                   None if sk is None else sk.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                   recs, nrec, C.byref(nr))
+        res.append((t.value, h.value, steps.value, total.value, rc, unpad(g, x),
+                    [(r.eps, (r.q, r.k, r.j, r.i)) for r in recs[:nr.value]]))
     return res
 
 

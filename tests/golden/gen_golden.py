@@ -35,6 +35,10 @@ Cases (SURVEY.md section 4.2 KATs 1-4):
   g400     BASELINE configs[2]: grid_nodes 400 (200x200x400, 16 M cells), calc_mode 0 to
            t = 0.002 and 0.005 s (about 45 and 67 attempted steps); run on 8 MPI ranks and checked
            identical on 5 (about 3 minutes of the build container's 8 cores).
+  epsctl   the inputs of the step-size decision that the default driver never changes, on the ctl
+           case's grid from its IC to t = 36 s: DELTA_LOCAL (hybrid2.c:578), per-variable
+           chunk_eps_mult (0.25, 3, 7) (hybrid2.c:521), both, and multipliers that vary inside a
+           variable (x1 on even planes, x2.5 on odd ones); each checked identical on 3 ranks.
 
     python tests/golden/gen_golden.py [case ...]     (default: all)
 """
@@ -78,10 +82,11 @@ class Work:
         with open(os.path.join(self.dir, "Params"), "w") as f:
             f.write(params_text(replace))
 
-    def run(self, nranks, *args, timeout=600):
-        out = os.path.join(self.dir, f"out{nranks}_{abs(hash(args)) % 10**8}")
+    def run(self, nranks, *args, timeout=600, opts=()):
+        """opts: the harness options that precede the command (--delta, --mult, --mult-odd-planes)"""
+        out = os.path.join(self.dir, f"out{nranks}_{abs(hash(args + tuple(opts))) % 10**8}")
         os.makedirs(out, exist_ok=True)
-        cmd = [PFT_REF, args[0], "Params", out] + [str(a) for a in args[1:]]
+        cmd = [PFT_REF] + [str(o) for o in opts] + [args[0], "Params", out] + [str(a) for a in args[1:]]
         if nranks > 1:
             cmd = [MPIRUN, "-np", str(nranks)] + cmd
         subprocess.run(cmd, cwd=self.dir, env=ENV, check=True, timeout=timeout,
@@ -402,6 +407,56 @@ def case_ctl():
     return arrays, meta
 
 
+EPSCTL_MULT = (0.25, 3.0, 7.0)
+EPSCTL_ODD = 2.5
+
+
+def case_epsctl():
+    """The reference's solvex with a delta mode and chunk multipliers other than the driver's
+    (DELTA_GLOBAL, 1): runs a-d of the docstring above, rows (t, h, steps, steps_total, rc) and the
+    final state of each"""
+    arrays, meta = {}, {"case": "epsctl", "source": "reference Params, grid_nodes 20, solvex with options",
+                        "mult": list(EPSCTL_MULT), "mult_odd_planes": EPSCTL_ODD}
+    w = Work({"grid_nodes": 20})
+    try:
+        out = w.run(1, "setup")
+        p = read_params(out)
+        shape = (3, p["n3"], p["n2"], p["n1"])
+        ic = load(os.path.join(out, "ic.f64"), shape)
+        meta["params"] = hexify(p)
+        arrays["ic"] = ic
+        icp = os.path.join(w.dir, "ic.f64")
+        ic.tofile(icp)
+        T = 36.0                       # g20's and ctl's first traj_times entry
+        meta["T"] = T
+        mult = ",".join(repr(v) for v in EPSCTL_MULT)
+        spec = {
+            "a": {"delta_local": True, "mult": None, "odd": None, "opts": ["--delta", "local"]},
+            "b": {"delta_local": False, "mult": list(EPSCTL_MULT), "odd": None, "opts": ["--mult", mult]},
+            "c": {"delta_local": True, "mult": list(EPSCTL_MULT), "odd": None,
+                  "opts": ["--delta", "local", "--mult", mult]},
+            "d": {"delta_local": False, "mult": None, "odd": EPSCTL_ODD,
+                  "opts": ["--mult-odd-planes", repr(EPSCTL_ODD)]},
+        }
+        runs = {}
+        for name, sp in spec.items():
+            o = w.run(1, "solvex", icp, 0.0, 1.0, 0, -1, T, opts=sp["opts"])
+            tm, _, states = traj_ext(o, 1, shape)
+            o3 = w.run(3, "solvex", icp, 0.0, 1.0, 0, -1, T, opts=sp["opts"])
+            tm3, _, states3 = traj_ext(o3, 1, shape)
+            assert tm == tm3 and np.array_equal(states[0], states3[0]), f"decomposition invariance ({name})"
+            runs[name] = {"delta_local": sp["delta_local"], "mult": sp["mult"], "mult_odd_planes": sp["odd"],
+                          "t0": 0.0, "h0": 1.0, "traj": [r[:5] for r in tm]}
+            arrays[f"{name}_state0"] = states[0]
+        # the options are seen: no two runs end with the same step record
+        recs = [tuple(map(tuple, r["traj"])) for r in runs.values()]
+        assert len(set(recs)) == len(recs), recs
+        meta["runs"] = runs
+    finally:
+        w.close()
+    return arrays, meta
+
+
 def case_ragged():
     arrays, meta = {}, {"case": "ragged", "source": "reference Params, L1=0.036 L2=0.024 grid_nodes 30"}
     rep = {"L1": 0.036, "L2": 0.024, "grid_nodes": 30}
@@ -452,7 +507,7 @@ def main():
     if not os.path.exists(PFT_REF):
         sys.exit("build the reference harness first: make -C oracle ref")
     cases = {"g20": case_g20, "ragged": case_ragged, "g100": case_g100, "ctl": case_ctl, "g200": case_g200,
-             "g400": case_g400, "g20nf": case_g20nf, "gnoise": case_gnoise}
+             "g400": case_g400, "g20nf": case_g20nf, "gnoise": case_gnoise, "epsctl": case_epsctl}
     for name in sys.argv[1:] or list(cases):
         arrays, meta = cases[name]()
         name = meta["case"]
