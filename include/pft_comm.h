@@ -109,6 +109,11 @@ int pft_comm_eps_host(pft_comm * c, double * eps, int * nonfinite);
 int pft_comm_eps_publish(pft_comm * c);
 /* host-level collectives used outside the per-stage path */
 int pft_comm_bcast(pft_comm * c, void * data, int bytes, int root);
+/* every rank's `bytes` (<= 256, as pft_comm_bcast) into all[rank * bytes ...] on every rank, in rank
+   order: ipc one shared-memory round, loopback the group's buffer between two barriers, RCCL
+   ncclAllGather on the communication stream through pinned host memory (its bounded, watched
+   wait); a single rank copies.  PFT_ERR_COMM_ABORTED on an aborted communicator, -2 bad arguments. */
+int pft_comm_allgather(pft_comm * c, const void * mine, int bytes, void * all);
 int pft_comm_allreduce_max_i64(pft_comm * c, long long * v);
 int pft_comm_barrier(pft_comm * c);
 

@@ -20,6 +20,8 @@
 
 #include <stddef.h>
 
+#include "pft_diag.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -138,6 +140,22 @@ int pft_slab_order(pft_slab * s, int comm_first);
 /* host layout (reference padded, ghost thickness 2) <-> device layout, on the compute stream */
 int pft_slab_upload_host(pft_slab * s, int which, const double * host_padded);
 int pft_slab_download_host(pft_slab * s, int which, double * host_padded);
+
+/* f5: the ice diagnostics (pft_diag.h) of interior planes 1..n3 of buffer `buf`, by one reduction
+   kernel on the compute stream -- ordered after everything queued there; no ghost plane is read.
+   Bit for bit pft_diag_host of the same state: counts are 64-bit integer atomics, maxima and
+   minima go through an order-preserving integer key (no floating-point atomics), so the result
+   depends on neither the grid nor the order of arrival; the accumulators are zeroed on the stream
+   by every call.  The record (and ice_per_plane: optional, n3 entries, the ice count of each
+   interior plane) arrives through pinned host memory; the host wait is the slab's bounded one
+   (pft_slab_sync below: PFT_ERR_IPC_TIMEOUT / PFT_ERR_COMM_ABORTED, never a hang).  opts = NULL:
+   thresholds 0.5.  Env PFT_DIAG_WGS=n (read at pft_slab_create) caps the kernel's workgroups
+   (default 8 per CU; A/B and tests). */
+int pft_slab_diag(pft_slab * s, int buf, const pft_diag_opts * opts, pft_diag * out, long long * ice_per_plane);
+/* HIP-event timing of that kernel alone (scripts/diag_time.py): timing(s, 1) records an event
+   before and after the kernel of every later call, last_ms the elapsed time of the last call's */
+int pft_slab_diag_timing(pft_slab * s, int on);
+int pft_slab_diag_last_ms(pft_slab * s, double * ms);
 
 /* One Merson stage (stage 1..5) as ONE fused kernel: K = f(stage input) and the pointwise stage
    combine of RK_MPI_SAsolver_hybrid2.c:378-450 (stage 5: error norm :507-524 and the candidate

@@ -31,6 +31,22 @@ int pft_solve_ex(FLOAT final_time, RK_MPI_S_SOLUTION * system, long max_steps_to
    reads only t and h. */
 int pft_solver_download(RK_MPI_S_SOLUTION * system);
 
+/* f5: the ice diagnostics (pft_diag.h; opts = NULL: thresholds 0.5) of the device-resident x of
+   the fused path -- the published ice fraction is global->ice / global->cells -- without a
+   download: one reduction kernel per slab (pft_slab_diag) and 96 bytes per rank.  Valid after any
+   fused solve (RK_MPI_SA_solve or pft_solve_ex) and after a device IC.  global: the whole grid's
+   record, the same bits on every rank; local (optional): this slab's; ice_per_plane (optional,
+   this slab's n3 entries): the ice count of each of its planes, global rows first_row + k.
+   Collective when the communicator has several ranks: the records are gathered
+   (pft_comm_allgather) and merged in rank order, each with its rank's status, so every rank
+   returns the same code.  From inside a Service_Callback it describes the state of the step just
+   accepted, under the contract of pft_solver_download -- on one rank; with several ranks it
+   refuses with -2 there (another rank's callback need not make the same call).
+   0; -3: no initialised solver, or no resident state (before the first fused solve with a host IC;
+   on the host-staged path) -- never stale numbers; -2: global is NULL, or see above;
+   PFT_SOLVE_DEVICE_ERROR (below). */
+int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * local, long long * ice_per_plane);
+
 /* f1 (after RK_MPI_SA_init): the default Params' initial condition (Params:9-21,
    intertrack.c:1880-2010) and, with with_beads, the glass beads (PrecalculateData,
    equation.c:459-530) computed on the device straight into the solver's state, bit for bit what

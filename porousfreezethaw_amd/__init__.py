@@ -84,6 +84,25 @@ class pft_solver_stats(C.Structure):
                 ("gated_steps", C.c_long), ("gate_misses", C.c_long)]
 
 
+class pft_diag_opts(C.Structure):
+    """include/pft_diag.h: the thresholds (the published scripts': 0.5, 0.5)"""
+    _fields_ = [("p_thr", C.c_double), ("gl_thr", C.c_double)]
+
+
+class pft_diag(C.Structure):
+    """include/pft_diag.h: the ice diagnostics of a state -- counts and maxima, exact"""
+    _fields_ = [("cells", C.c_longlong), ("ice", C.c_longlong), ("pore", C.c_longlong),
+                ("ice_pore", C.c_longlong), ("nonfinite", C.c_longlong), ("ice_u_maxabs", C.c_double),
+                ("u_min", C.c_double), ("u_max", C.c_double), ("p_min", C.c_double), ("p_max", C.c_double)]
+
+    def as_dict(self):
+        """the fields and ice_fraction = ice / cells (correctly rounded: what ncwa gets from an
+        exact sum of 0/1 values)"""
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["ice_fraction"] = d["ice"] / d["cells"] if d["cells"] else float("nan")
+        return d
+
+
 _lib = None
 
 
@@ -163,6 +182,15 @@ def lib():
         L.pft_snapshot_read_info.argtypes = [C.c_char_p, ip, ip, ip, sp, dp]
         L.pft_snapshot_read_slab.argtypes = [C.c_char_p, gp, dp]
         L.pft_snapshot_title.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_double]
+        op, dgp, llp = C.POINTER(pft_diag_opts), C.POINTER(pft_diag), C.POINTER(C.c_longlong)
+        L.pft_diag_host.argtypes = [gp, dp, op, dgp, llp]
+        L.pft_diag_combine.argtypes = [dgp, dgp]
+        L.pft_slab_diag.argtypes = [C.c_void_p, C.c_int, op, dgp, llp]
+        L.pft_slab_diag_timing.argtypes = [C.c_void_p, C.c_int]
+        L.pft_slab_diag_last_ms.argtypes = [C.c_void_p, dp]
+        L.pft_solver_diag.argtypes = [op, dgp, dgp, llp]
+        L.pft_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.pft_comm_size.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -208,6 +236,24 @@ def comm_destroy(c):
 def params_array(values):
     """dict name -> value  ->  param[] in model.c order"""
     return np.array([float(values[k]) for k in PARAM_NAMES], dtype=np.float64)
+
+
+def series_times(t0, final_time, saved_files):
+    """the snapshot times of the driver's loop (intertrack.c:2265-2283 with starting_snapshot 0):
+    snapshot 0 is t0 itself, snapshot s is t0 + ((final_time - t0) * s) / (saved_files - 1), in
+    that operation order in double"""
+    t0, final_time, saved_files = float(t0), float(final_time), int(saved_files)
+    if saved_files < 1:
+        raise ValueError(f"saved_files must be at least 1, not {saved_files}")
+    return [t0] + [t0 + ((final_time - t0) * float(s)) / float(saved_files - 1) for s in range(1, saved_files)]
+
+
+def write_series_txt(rows, path, key="ice_fraction"):
+    """one value per line as "%.15g \n" (with the trailing blank): the format of the published
+    series files (0.03488 , 0.055108 ); rows: run_series' rows, or any dicts with `key`"""
+    with open(path, "w") as f:
+        for r in rows:
+            f.write("%.15g \n" % r[key])
 
 
 class Simulation:
@@ -373,6 +419,113 @@ class Simulation:
         rc = self.lib.pft_solver_download(C.byref(self.system))
         if rc:
             raise RuntimeError(f"pft_solver_download failed ({rc})")
+
+    # -- f5: diagnostics and the driver's snapshot loop ------------------------------------------
+    def _diag_host_global(self, o, planes):
+        """pft_diag_host of self.x, merged over the communicator's ranks in rank order (collective)"""
+        L_ = self.lib
+        mine = pft_diag()
+        rc = L_.pft_diag_host(C.byref(self.grid), _dp(self.x), C.byref(o), C.byref(mine), planes)
+        if rc:
+            raise RuntimeError(f"pft_diag_host failed ({rc})")
+        comm = L_.pft_comm_current()
+        n = L_.pft_comm_size(comm) if comm else 1
+        if n == 1:
+            return mine, mine
+        every = (pft_diag * n)()
+        rc = L_.pft_comm_allgather(comm, C.byref(mine), C.sizeof(pft_diag), every)
+        if rc:
+            raise RuntimeError(f"pft_comm_allgather failed ({rc})")
+        glob = pft_diag.from_buffer_copy(every[0])
+        for r in range(1, n):
+            L_.pft_diag_combine(C.byref(glob), C.byref(every[r]))
+        return glob, mine
+
+    def diagnostics(self, p_thr=0.5, gl_thr=0.5, where="device", per_plane=False):
+        """The ice diagnostics (include/pft_diag.h) of the whole grid as a dict: the struct's fields
+        and ice_fraction = ice / cells, the published quantity (scripts/avg.sh).  where="device":
+        of the device-resident state, by pft_solver_diag -- no download; collective on several
+        ranks; RuntimeError when nothing is resident (before the first fused solve with a host
+        IC).  where="host": pft_diag_host of self.x, merged over the ranks (collective too).
+        per_plane: also ice_per_plane (this rank's planes) and first_row, and "local", this
+        slab's own record."""
+        if where not in ("device", "host"):
+            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
+        d = self._diagnostics(p_thr, gl_thr, where, per_plane)
+        if d is None:
+            raise RuntimeError("diagnostics: no state is resident on the device (no initialised solver, or no "
+                               "fused solve or device IC yet); solve first, or use where='host'")
+        return d
+
+    def _diagnostics(self, p_thr, gl_thr, where, per_plane):
+        """diagnostics(); None when where="device" and nothing is resident (pft_solver_diag's -3,
+        the same on every rank)"""
+        o = pft_diag_opts(p_thr, gl_thr)
+        planes = (C.c_longlong * self.grid.n3)() if per_plane else None
+        if where == "host":
+            glob, mine = self._diag_host_global(o, planes)
+        else:
+            glob, mine = pft_diag(), pft_diag()
+            rc = self.lib.pft_solver_diag(C.byref(o), C.byref(glob), C.byref(mine), planes)
+            if rc == -3:
+                return None
+            if rc:
+                raise RuntimeError(f"pft_solver_diag failed ({rc}): {self.lib.pft_hip_last_error()}")
+        d = glob.as_dict()
+        if per_plane:
+            d["ice_per_plane"] = np.array(planes[:], dtype=np.int64)
+            d["first_row"] = self.grid.first_row
+            d["local"] = mine.as_dict()
+        return d
+
+    def run_series(self, final_time=None, saved_files=None, times=None, snapshot_path=None, comment="",
+                   diag=True, opts=None):
+        """The driver's snapshot loop (intertrack.c:2265-2283).  Snapshot 0 is the state as it
+        stands (no solve); snapshot s solves to series_times(t0, final_time, saved_files)[s], or
+        to times[s - 1] when times= lists the solve targets.  The steps run device-resident
+        (pft_solve_ex with KEEP_DEVICE | REUSE_DEVICE: nothing crosses PCIe between snapshots; the
+        first call uploads unless the IC is already on the device).  Returns one dict per
+        snapshot: snapshot, t, h, steps, steps_total, rc (None for snapshot 0) and, with diag,
+        the global diagnostics (opts: a (p_thr, gl_thr) pair).  snapshot_path: every snapshot is
+        also downloaded and written to "<snapshot_path>.%03d.ncd" with the reference's snapshot /
+        total_snapshots attributes.  Collective on several ranks.  A solve that returns 1 (a
+        Service_Callback break) ends the series with that row."""
+        t0 = self.system.t
+        if times is not None:
+            targets = [t0] + [float(t) for t in times]
+        else:
+            if final_time is None or saved_files is None:
+                raise ValueError("run_series needs final_time and saved_files, or times=")
+            targets = series_times(t0, final_time, saved_files)
+        p_thr, gl_thr = opts if opts is not None else (0.5, 0.5)
+        end = targets[-1] if final_time is None else float(final_time)
+        rows = []
+        for s, T in enumerate(targets):
+            rc = None
+            if s > 0:
+                rc = self.solve_ex(T, 0, PFT_SOLVE_KEEP_DEVICE | PFT_SOLVE_REUSE_DEVICE)
+            row = {"snapshot": s, "t": self.system.t, "h": self.system.h, "steps": self.system.steps,
+                   "steps_total": self.system.steps_total, "rc": rc}
+            if diag:
+                d = self._diagnostics(p_thr, gl_thr, "device", False)
+                if d is None and s == 0:
+                    # snapshot 0 of a host IC: the state is still the host array
+                    d = self._diagnostics(p_thr, gl_thr, "host", False)
+                if d is None:
+                    raise RuntimeError("run_series: no state is resident on the device after the solve "
+                                       "(the host-staged path keeps none)")
+                row.update(d)
+            if snapshot_path is not None:
+                drc = self.lib.pft_solver_download(C.byref(self.system))
+                if drc and not (drc == -2 and s == 0):   # -2 at snapshot 0: a host IC, nothing resident yet
+                    raise RuntimeError(f"pft_solver_download failed ({drc})")
+                info = snapshot_info(self.system.t, self.system.h, end, self.system.delta, self.grid.calc_mode,
+                                     snapshot=s, total_snapshots=len(targets), comment=comment)
+                save_snapshot(self, "%s.%03d.ncd" % (snapshot_path, s), info)
+            rows.append(row)
+            if rc == 1:
+                break
+        return rows
 
     def tile_geometry(self):
         """{stage: (kernel kind, wx cell pairs, ty rows)} of the slab's stage launches (kind 0 cache,

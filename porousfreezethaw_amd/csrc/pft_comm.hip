@@ -63,6 +63,7 @@ struct LoopGroup {
   unsigned long long* eps;   // 2 per rank
   long long* ivals;          // 1 per rank
   char bbuf[256];
+  char* abuf;                // 256 per rank (pft_comm_allgather)
 };
 
 struct pft_comm {
@@ -86,6 +87,8 @@ struct pft_comm {
   int ce;                    // ipc: the halo planes go on the copy engines beside the interior launch
                              // (pft_comm_set_copy_engine; env PFT_IPC_CE)
   void* bcast_pinned;        // rccl: pinned host staging of pft_comm_bcast
+  void* ag_dev;              // rccl: 256 bytes per rank of device memory and their pinned host
+  void* ag_pinned;           // staging (pft_comm_allgather), allocated by its first call
   // rccl: every host wait on RCCL work is bounded (PFT_COMM_TIMEOUT, default 300 s) and watches
   // ncclCommGetAsyncError; on expiry or an error the communicator is aborted (ncclCommAbort) and
   // every later call refuses (PFT_ERR_COMM_ABORTED)
@@ -368,6 +371,7 @@ int pft_comm_init_loopback(pft_comm** group, int nranks)
   g->slabs = (pft_slab**)calloc(nranks, sizeof(pft_slab*));
   g->eps = (unsigned long long*)calloc(2 * nranks, sizeof(unsigned long long));
   g->ivals = (long long*)calloc(nranks, sizeof(long long));
+  g->abuf = (char*)calloc(nranks, 256);
   m->grp = g;
   *group = m;
   return 0;
@@ -404,11 +408,14 @@ int pft_comm_destroy(pft_comm* c)
     munmap(c->shm, sizeof(IpcShared));
   }
   if (c->bcast_pinned) (void)hipHostFree(c->bcast_pinned);
+  if (c->ag_pinned) (void)hipHostFree(c->ag_pinned);
+  if (c->ag_dev) (void)hipFree(c->ag_dev);
   if (c->kind == KIND_LOOP && c->rank < 0) {
     pthread_barrier_destroy(&c->grp->bar);
     free(c->grp->slabs);
     free(c->grp->eps);
     free(c->grp->ivals);
+    free(c->grp->abuf);
     free(c->grp);
   }
   free(c);
@@ -774,6 +781,45 @@ int pft_comm_bcast(pft_comm* c, void* data, int bytes, int root)
   if (c->rank == root) memcpy(c->grp->bbuf, data, bytes);
   loop_barrier(c);
   if (c->rank != root) memcpy(data, c->grp->bbuf, bytes);
+  loop_barrier(c);
+  return 0;
+}
+
+int pft_comm_allgather(pft_comm* c, const void* mine, int bytes, void* all)
+{
+  if (!mine || !all || bytes < 1 || bytes > 256) return -2;
+  if (!c || c->size == 1) {
+    memcpy(all, mine, bytes);
+    return 0;
+  }
+  if (c->kind == KIND_IPC) {
+    IpcRound* R;
+    int rc = ipc_round(c, nullptr, 0, mine, bytes, &R);
+    if (rc) return rc;
+    for (int q = 0; q < c->size; ++q) memcpy((char*)all + (size_t)q * bytes, R[q].bytes, bytes);
+    return 0;
+  }
+  if (c->kind == KIND_RCCL) {
+    // as pft_comm_bcast: on the communication stream through pinned host memory, so that the host
+    // waits for that stream only
+    if (c->aborted) return PFT_ERR_COMM_ABORTED;
+    hipStream_t st = c->slab ? (hipStream_t)pft_slab_comm_stream(c->slab) : 0;
+    if (!c->ag_pinned) HCHK(hipHostMalloc(&c->ag_pinned, 256 * (size_t)c->size, hipHostMallocDefault));
+    if (!c->ag_dev) HCHK(hipMalloc(&c->ag_dev, 256 * (size_t)c->size));
+    char* pin = (char*)c->ag_pinned;
+    char* dev = (char*)c->ag_dev;
+    memcpy(pin + (size_t)c->rank * bytes, mine, bytes);
+    HCHK(hipMemcpyAsync(dev + (size_t)c->rank * bytes, pin + (size_t)c->rank * bytes, bytes, hipMemcpyHostToDevice, st));
+    NCCLCHK(ncclAllGather(dev + (size_t)c->rank * bytes, dev, bytes, ncclUint8, c->nccl, st));
+    HCHK(hipMemcpyAsync(pin, dev, (size_t)bytes * c->size, hipMemcpyDeviceToHost, st));
+    const int rc = rccl_stream_wait(c, st);
+    if (rc) return rc;
+    memcpy(all, pin, (size_t)bytes * c->size);
+    return 0;
+  }
+  memcpy(c->grp->abuf + 256 * (size_t)c->rank, mine, bytes);
+  loop_barrier(c);
+  for (int q = 0; q < c->size; ++q) memcpy((char*)all + (size_t)q * bytes, c->grp->abuf + 256 * (size_t)q, bytes);
   loop_barrier(c);
   return 0;
 }

@@ -2351,6 +2351,13 @@ struct pft_slab {
   int pair_env;          // PFT_PAIR was set
   int pair_tx, pair_ty;  // pair tile (pair_geometry, once per slab); 0 x 0: none fits
   long pair_ntile;
+  // f5 diagnostics (pft_slab_diag): device accumulators (PFT_DIAG_HEAD words, then one ice count
+  // per interior plane) and their pinned host copy, allocated by the first call
+  unsigned long long* diag_dev;
+  unsigned long long* diag_host;     // pinned
+  int diag_wgs;          // cap on the reduction's workgroups; 0: 8 per CU (env PFT_DIAG_WGS: A/B, tests)
+  int diag_timing;       // 1: HIP events around the kernel (pft_slab_diag_timing)
+  hipEvent_t ev_diag[2];
   double timeout_s;      // bound on a host wait for the compute stream while ipc peers are on
                          // (env PFT_IPC_TIMEOUT, default 300 s; slab_wait)
   pft_slab_watch_fn watch;   // communicator watchdog (RCCL: async error / expiry -> abort)
@@ -2584,6 +2591,8 @@ int pft_slab_create(pft_slab** out, const pft_slab_desc* d, const pft_consts* c)
     s->wait_streamops = ew ? atoi(ew) : 0;
     const char* et = getenv("PFT_IPC_TIMEOUT");
     s->timeout_s = (et && atof(et) > 0.0) ? atof(et) : 300.0;
+    const char* edg = getenv("PFT_DIAG_WGS");
+    s->diag_wgs = (edg && atoi(edg) > 0) ? atoi(edg) : 0;
   }
   const size_t bytes = sizeof(double) * (3 * (size_t)s->fs + 2 * (size_t)s->plane);
   hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
@@ -2661,6 +2670,10 @@ int pft_slab_destroy(pft_slab* s)
     for (int e = 0; e < 2; ++e)
       for (int r = 0; r < PFT_TRING; ++r)
         if (s->tev[st][r][e]) (void)hipEventDestroy(s->tev[st][r][e]);
+  if (s->diag_dev) (void)hipFree(s->diag_dev);
+  if (s->diag_host) (void)hipHostFree(s->diag_host);
+  for (int i = 0; i < 2; ++i)
+    if (s->ev_diag[i]) (void)hipEventDestroy(s->ev_diag[i]);
   if (s->scratch) (void)hipFree(s->scratch);
   if (s->host_scratch) (void)hipHostFree(s->host_scratch);
   if (s->host_pub) (void)hipHostFree(s->host_pub);
@@ -2748,6 +2761,299 @@ int pft_slab_download_host(pft_slab* s, int which, double* host_padded)
   HIPCHK(hipMemcpyAsync(host_padded, s->staging, sizeof(double) * 3 * (size_t)s->S, hipMemcpyDeviceToHost,
                         s->stream));
   return slab_wait(s, nullptr, "download");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// f5: the ice diagnostics of a state (pft_diag.h) -- a streaming reduction over the interior of
+// the three fields, each one contiguous run of n = n3 * plane doubles from plane 1 (no x/y ghosts).
+//
+// Everything is an integer: counts are added as 64-bit integers, maxima and minima go through
+// diag_key, a 64-bit key that orders every non-NaN double as the double orders (and -0.0 below
+// +0.0), so the same bits come out for any grid, chunking or arrival order.  Key 0 belongs to no
+// non-NaN double: a zeroed accumulator means "no value yet", and the minimum is kept as the maximum
+// of the complemented key, so one hipMemsetAsync per call resets every word.
+//
+// Work: the run is cut into 16-byte pairs (pair q = elements 2q - head, 2q - head + 1; head = 1
+// if the run started on an odd multiple of 8 bytes -- with the slab's layout it does not -- and the
+// first and the last pair may hold one element).  Workgroup b takes per_wg consecutive pairs and
+// indexes its elements from its first pair's (32-bit r); per iteration each wave takes 512
+// consecutive elements, four 16-byte loads per lane and field, all issued before the first use, so
+// a wave meets the planes in ascending order.  Where the 512 lie inside the run (all but the first
+// and last iteration of the grid) no element is tested for validity; elsewhere each is loaded alone
+// under its own test.  Counts come from __ballot and popcount and stay in scalar registers; the ice
+// count of the iteration goes to its plane -- one add when the 512 elements lie in one plane, else
+// one ballot round per plane touched -- into an LDS window of the workgroup's first PFT_DIAG_WIN
+// planes (past the window: the plane's global word).  At the end the keys are reduced across the
+// lanes and, through LDS, across the four waves: one set of global atomics per workgroup, plus
+// one per plane it touched.  (A first version with one pair per lane and iteration and 64-bit
+// bookkeeping ran at 3.5 TB/s, bound by scalar instruction issue: DESIGN.md section 7, f5.)
+#define PFT_DBLOCK 256
+#define PFT_DIAG_UNROLL 4                               // 16-byte loads per lane, field and iteration
+#define PFT_DIAG_WAVE_ELEMS (128 * PFT_DIAG_UNROLL)    // elements of a wave's iteration
+#define PFT_DIAG_WG_PAIRS (PFT_DBLOCK * PFT_DIAG_UNROLL)
+#define PFT_DIAG_HEAD 16   // accumulator words before the per-plane counts
+#define PFT_DIAG_WIN 64
+enum { DG_ICE = 0, DG_PORE, DG_ICE_PORE, DG_NONFINITE, DG_ICE_U, DG_U_MAX, DG_U_MIN, DG_P_MAX, DG_P_MIN, DG_WORDS };
+
+__host__ __device__ static inline unsigned long long diag_key(double x)
+{
+  unsigned long long b;
+  memcpy(&b, &x, 8);
+  return (b >> 63) ? ~b : (b | (1ULL << 63));
+}
+static double diag_unkey(unsigned long long k)
+{
+  const unsigned long long b = (k >> 63) ? (k & ~(1ULL << 63)) : ~k;
+  double x;
+  memcpy(&x, &b, 8);
+  return x;
+}
+
+__device__ __forceinline__ bool diag_finite(double x) { return fabs(x) < __builtin_inf(); }   // false on NaN
+
+struct DiagState {
+  unsigned long long c_ice, c_pore, c_both, c_nf;     // wave-uniform counts
+  unsigned long long iu, umax, umin, pmax, pmin;      // per-lane keys
+  int k, lo, hi;   // the wave's running plane: index from the workgroup's first, elements [lo, hi) (r)
+};
+
+// one iteration of a wave: elements r0 .. r0 + 511 of the workgroup (of them [r_lo, r_hi) exist;
+// FULL: all do).  fu/fp/fg point at the workgroup's element 0.
+template <bool FULL>
+__device__ __forceinline__ void diag_iter(DiagState& st, const double* __restrict__ fu, const double* __restrict__ fp,
+                                          const double* __restrict__ fg, int r0, int r_lo, int r_hi, int plane,
+                                          int lane, double p_thr, double gl_thr, unsigned long long* s_win,
+                                          unsigned long long* __restrict__ acc_planes)
+{
+  constexpr int NE = 2 * PFT_DIAG_UNROLL;
+  double u[NE], p[NE], g[NE];
+  bool v[NE], ice[NE];
+#pragma unroll
+  for (int j = 0; j < PFT_DIAG_UNROLL; ++j) {
+    const int r = r0 + 128 * j + 2 * lane;
+    if (FULL) {
+      const double2 a = *reinterpret_cast<const double2*>(fu + r);
+      const double2 b = *reinterpret_cast<const double2*>(fp + r);
+      const double2 c = *reinterpret_cast<const double2*>(fg + r);
+      u[2 * j] = a.x, u[2 * j + 1] = a.y, p[2 * j] = b.x, p[2 * j + 1] = b.y, g[2 * j] = c.x, g[2 * j + 1] = c.y;
+      v[2 * j] = v[2 * j + 1] = true;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const bool ok = r + i >= r_lo && r + i < r_hi;
+        v[2 * j + i] = ok;
+        u[2 * j + i] = ok ? fu[r + i] : 0.0;
+        p[2 * j + i] = ok ? fp[r + i] : 0.0;
+        g[2 * j + i] = ok ? fg[r + i] : 0.0;
+      }
+    }
+  }
+  unsigned it_ice = 0;
+#pragma unroll
+  for (int i = 0; i < NE; ++i) {
+    // ordered comparisons: false on NaN
+    ice[i] = v[i] && p[i] > p_thr;
+    const bool por = v[i] && g[i] < gl_thr;
+    const bool nf = v[i] && !(diag_finite(u[i]) && diag_finite(p[i]) && diag_finite(g[i]));
+    it_ice += (unsigned)__popcll(__ballot(ice[i]));
+    st.c_pore += __popcll(__ballot(por));
+    st.c_both += __popcll(__ballot(ice[i] && por));
+    st.c_nf += __popcll(__ballot(nf));
+    if (v[i] && u[i] == u[i]) {
+      const unsigned long long k = diag_key(u[i]);
+      st.umax = k > st.umax ? k : st.umax;
+      st.umin = ~k > st.umin ? ~k : st.umin;
+      if (ice[i]) {
+        const unsigned long long a = (unsigned long long)__double_as_longlong(fabs(u[i]));
+        st.iu = a > st.iu ? a : st.iu;   // non-negative doubles order as their bits
+      }
+    }
+    if (v[i] && p[i] == p[i]) {
+      const unsigned long long k = diag_key(p[i]);
+      st.pmax = k > st.pmax ? k : st.pmax;
+      st.pmin = ~k > st.pmin ? ~k : st.pmin;
+    }
+  }
+  st.c_ice += it_ice;
+  // the ice counts of the planes the wave's existing elements [w0, w1] lie in
+  const int w0 = FULL ? r0 : (r0 > r_lo ? r0 : r_lo);
+  const int w1 = (FULL ? r0 + PFT_DIAG_WAVE_ELEMS : (r0 + PFT_DIAG_WAVE_ELEMS < r_hi ? r0 + PFT_DIAG_WAVE_ELEMS : r_hi)) - 1;
+  if (w1 < w0) return;
+  while (w0 >= st.hi) {
+    ++st.k;
+    st.lo = st.hi;
+    st.hi += plane;
+  }
+  const bool one_plane = w1 < st.hi;
+  while (true) {
+    unsigned c = it_ice;
+    if (!one_plane) {
+      c = 0;
+#pragma unroll
+      for (int i = 0; i < NE; ++i) {
+        const int r = r0 + 128 * (i >> 1) + 2 * lane + (i & 1);
+        c += (unsigned)__popcll(__ballot(ice[i] && r >= st.lo && r < st.hi));
+      }
+    }
+    if (lane == 0 && c) {
+      if (st.k < PFT_DIAG_WIN)
+        atomicAdd(&s_win[st.k], (unsigned long long)c);
+      else
+        atomicAdd(&acc_planes[st.k], (unsigned long long)c);
+    }
+    if (w1 < st.hi) break;
+    ++st.k;
+    st.lo = st.hi;
+    st.hi += plane;
+  }
+}
+
+__global__ __launch_bounds__(PFT_DBLOCK) void diag_kernel(const double* __restrict__ fu, const double* __restrict__ fp,
+                                                          const double* __restrict__ fg, long n, int plane, int head,
+                                                          long nq, long per_wg, double p_thr, double gl_thr,
+                                                          unsigned long long* __restrict__ acc)
+{
+  __shared__ unsigned long long s_win[PFT_DIAG_WIN];
+  __shared__ unsigned long long s_red[PFT_DBLOCK / 64][DG_WORDS];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long q_begin = (long)blockIdx.x * per_wg;
+  const long q_end = q_begin + per_wg < nq ? q_begin + per_wg : nq;
+  for (int i = threadIdx.x; i < PFT_DIAG_WIN; i += PFT_DBLOCK) s_win[i] = 0;
+  __syncthreads();
+  // the workgroup's elements r = 0 .. span - 1 stand for e_base + r of the run; of them [r_lo, r_hi)
+  // exist (e_base = -1: the slot before the run; the last pair's second slot may lie past its end)
+  const long e_base = 2 * q_begin - head;
+  const int span = (int)(2 * (q_end - q_begin));
+  const int r_lo = e_base < 0 ? 1 : 0;
+  const int r_hi = n - e_base < span ? (int)(n - e_base) : span;
+  const long k_base = (e_base > 0 ? e_base : 0) / plane;   // the first plane this workgroup touches
+  DiagState st;
+  st.c_ice = st.c_pore = st.c_both = st.c_nf = 0;
+  st.iu = st.umax = st.umin = st.pmax = st.pmin = 0;
+  st.k = 0;
+  st.lo = (int)(k_base * plane - e_base);
+  st.hi = st.lo + plane;
+  const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
+  const double* wp = fp + e_base;
+  const double* wg = fg + e_base;
+  unsigned long long* acc_planes = acc + PFT_DIAG_HEAD + k_base;
+
+  for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
+    if (r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi)
+      diag_iter<true>(st, wu, wp, wg, r0, r_lo, r_hi, plane, lane, p_thr, gl_thr, s_win, acc_planes);
+    else
+      diag_iter<false>(st, wu, wp, wg, r0, r_lo, r_hi, plane, lane, p_thr, gl_thr, s_win, acc_planes);
+  }
+
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    unsigned long long o;
+    o = __shfl_xor(st.iu, off, 64), st.iu = o > st.iu ? o : st.iu;
+    o = __shfl_xor(st.umax, off, 64), st.umax = o > st.umax ? o : st.umax;
+    o = __shfl_xor(st.umin, off, 64), st.umin = o > st.umin ? o : st.umin;
+    o = __shfl_xor(st.pmax, off, 64), st.pmax = o > st.pmax ? o : st.pmax;
+    o = __shfl_xor(st.pmin, off, 64), st.pmin = o > st.pmin ? o : st.pmin;
+  }
+  if (lane == 0) {
+    unsigned long long* r = s_red[wave];
+    r[DG_ICE] = st.c_ice, r[DG_PORE] = st.c_pore, r[DG_ICE_PORE] = st.c_both, r[DG_NONFINITE] = st.c_nf;
+    r[DG_ICE_U] = st.iu, r[DG_U_MAX] = st.umax, r[DG_U_MIN] = st.umin, r[DG_P_MAX] = st.pmax, r[DG_P_MIN] = st.pmin;
+  }
+  __syncthreads();
+  if (threadIdx.x < DG_WORDS) {
+    // one thread per accumulator word: the waves' partials, then one atomic
+    const int w = threadIdx.x;
+    unsigned long long x = s_red[0][w];
+    for (int i = 1; i < PFT_DBLOCK / 64; ++i) {
+      const unsigned long long o = s_red[i][w];
+      x = w <= DG_NONFINITE ? x + o : (o > x ? o : x);
+    }
+    if (x) {
+      if (w <= DG_NONFINITE)
+        atomicAdd(&acc[w], x);
+      else
+        atomicMax(&acc[w], x);
+    }
+  }
+  if (threadIdx.x >= 64 && threadIdx.x < 64 + PFT_DIAG_WIN) {
+    const int t = threadIdx.x - 64;
+    const unsigned long long x = s_win[t];
+    if (x) atomicAdd(&acc_planes[t], x);
+  }
+}
+
+extern "C" {
+
+int pft_slab_diag(pft_slab* s, int buf, const pft_diag_opts* opts, pft_diag* out, long long* ice_per_plane)
+{
+  if (!s || !out || buf < 0 || buf >= PFT_BUF_COUNT) return -2;
+  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_diag");
+  const long plane = s->plane, n = (long)s->d.n3 * plane;
+  const size_t bytes = sizeof(unsigned long long) * (size_t)(PFT_DIAG_HEAD + s->d.n3);
+  if (!s->diag_dev) HIPCHK(hipMalloc((void**)&s->diag_dev, bytes));
+  if (!s->diag_host) HIPCHK(hipHostMalloc((void**)&s->diag_host, bytes, hipHostMallocDefault));
+  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
+  const double* fu = s->buf[buf] + plane;
+  const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
+  const long nq = (n + head + 1) / 2;
+  if (plane > (1L << 30)) return -2;   // (the kernel's 32-bit plane bounds)
+  // at most `cap` workgroups (all resident at once: 8 per CU), each a whole number of iterations
+  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
+  long wgs = (nq + PFT_DIAG_WG_PAIRS - 1) / PFT_DIAG_WG_PAIRS;
+  if (wgs > cap) wgs = cap;
+  const long wgs_min = (nq >> 29) + 1;   // a workgroup indexes its elements with 32 bits
+  if (wgs < wgs_min) wgs = wgs_min;
+  const long per_wg = ((nq + wgs - 1) / wgs + PFT_DIAG_WG_PAIRS - 1) / PFT_DIAG_WG_PAIRS * PFT_DIAG_WG_PAIRS;
+  wgs = (nq + per_wg - 1) / per_wg;
+  const double p_thr = opts ? opts->p_thr : 0.5, gl_thr = opts ? opts->gl_thr : 0.5;
+  // no state carries over between calls: every accumulator word is zeroed on the stream first
+  HIPCHK(hipMemsetAsync(s->diag_dev, 0, bytes, s->stream));
+  if (s->diag_timing) HIPCHK(hipEventRecord(s->ev_diag[0], s->stream));
+  diag_kernel<<<(unsigned)wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, n, (int)plane, head, nq, per_wg,
+                                                           p_thr, gl_thr, s->diag_dev);
+  HIPCHK(hipGetLastError());
+  if (s->diag_timing) HIPCHK(hipEventRecord(s->ev_diag[1], s->stream));
+  HIPCHK(hipMemcpyAsync(s->diag_host, s->diag_dev, bytes, hipMemcpyDeviceToHost, s->stream));
+  // the slab's bounded wait: an ipc peer's timeout or an aborted communicator ends it, as for the
+  // error norm
+  const int rc = slab_wait(s, nullptr, "pft_slab_diag");
+  if (rc) return rc;
+  const unsigned long long* h = s->diag_host;
+  out->cells = n;
+  out->ice = (long long)h[DG_ICE];
+  out->pore = (long long)h[DG_PORE];
+  out->ice_pore = (long long)h[DG_ICE_PORE];
+  out->nonfinite = (long long)h[DG_NONFINITE];
+  memcpy(&out->ice_u_maxabs, &h[DG_ICE_U], 8);
+  const double inf = __builtin_inf();
+  out->u_max = h[DG_U_MAX] ? diag_unkey(h[DG_U_MAX]) : -inf;
+  out->u_min = h[DG_U_MIN] ? diag_unkey(~h[DG_U_MIN]) : inf;
+  out->p_max = h[DG_P_MAX] ? diag_unkey(h[DG_P_MAX]) : -inf;
+  out->p_min = h[DG_P_MIN] ? diag_unkey(~h[DG_P_MIN]) : inf;
+  if (ice_per_plane)
+    for (int k = 0; k < s->d.n3; ++k) ice_per_plane[k] = (long long)h[PFT_DIAG_HEAD + k];
+  return 0;
+}
+
+int pft_slab_diag_timing(pft_slab* s, int on)
+{
+  if (!s) return -2;
+  for (int i = 0; i < 2 && on; ++i)
+    if (!s->ev_diag[i]) HIPCHK(hipEventCreate(&s->ev_diag[i]));
+  s->diag_timing = on ? 1 : 0;
+  return 0;
+}
+
+int pft_slab_diag_last_ms(pft_slab* s, double* ms)
+{
+  if (!s || !ms || !s->diag_timing) return -2;
+  float f = 0.0f;
+  HIPCHK(hipEventElapsedTime(&f, s->ev_diag[0], s->ev_diag[1]));
+  *ms = f;
+  return 0;
 }
 
 }  // extern "C"

@@ -706,6 +706,50 @@ int pft_solver_download(RK_MPI_S_SOLUTION * system)
 	return pft_slab_download_host(R.slab, PFT_BUF_X, system->x);
 }
 
+#define PFT_DIAG_MAX_RANKS 64   /* the ipc transport's limit (PFT_IPC_MAX) */
+
+int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * local, long long * ice_per_plane)
+{
+	/* f5: the diagnostics of the device-resident x.  Each rank reduces its slab; the records
+	   travel with the rank's status in one allgather and are merged in rank order, so every rank
+	   has the same record and returns the same code (a rank that failed locally still takes part,
+	   as in ic_device_finish) */
+	struct { long long status; pft_diag d; } mine, all[PFT_DIAG_MAX_RANKS];
+	pft_comm * c = comm();
+	const int nprocs = pft_comm_size(c);
+	int rc, r, bad = 0;
+	if(!global) return -2;
+	/* no initialised solver, or no resident state (before the first fused solve with a host IC,
+	   the host-staged path, after a failed call): no stale numbers */
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	/* inside a Service_Callback only one rank may ask: another rank's callback need not */
+	if(R.in_callback && nprocs > 1) return -2;
+	if(nprocs > PFT_DIAG_MAX_RANKS || sizeof(mine) > 256) return -2;
+	memset(&mine, 0, sizeof mine);
+	rc = pft_slab_diag(R.slab, PFT_BUF_X, opts, &mine.d, ice_per_plane);
+	mine.status = rc;
+	if(nprocs == 1) {
+		if(rc) { R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
+		*global = mine.d;
+		if(local) *local = mine.d;
+		return 0;
+	}
+	if((rc = pft_comm_allgather(c, &mine, (int)sizeof mine, all))) {
+		R.last_status = rc;
+		return PFT_SOLVE_DEVICE_ERROR;
+	}
+	for(r = 0; r < nprocs; r++) if(all[r].status) bad = 1;
+	if(bad) {
+		R.last_status = mine.status ? (int)mine.status : (int)all[0].status;
+		for(r = 0; r < nprocs && !R.last_status; r++) R.last_status = (int)all[r].status;
+		return PFT_SOLVE_DEVICE_ERROR;
+	}
+	*global = all[0].d;
+	for(r = 1; r < nprocs; r++) pft_diag_combine(global, &all[r].d);
+	if(local) *local = mine.d;
+	return 0;
+}
+
 /* the common end of the device IC paths: every rank's outcome agreed (a rank that failed locally
    still takes part, so that no other rank is left inside a collective: every rank returns the same,
    most negative, code), then the ghost planes exchanged as at an upload and gl_keep agreed */
