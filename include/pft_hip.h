@@ -21,6 +21,7 @@
 #include <stddef.h>
 
 #include "pft_diag.h"
+#include "pft_means.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -156,6 +157,24 @@ int pft_slab_diag(pft_slab * s, int buf, const pft_diag_opts * opts, pft_diag * 
    before and after the kernel of every later call, last_ms the elapsed time of the last call's */
 int pft_slab_diag_timing(pft_slab * s, int on);
 int pft_slab_diag_last_ms(pft_slab * s, double * ms);
+
+/* f6: the exact sums (pft_means.h) of interior planes 1..n3 of buffer `buf`: the raw words of
+   pft_means_host of the same state, word for word.  Two kernels on the compute stream, ordered
+   after everything queued there; no ghost plane is read.  means_kernel streams the three fields
+   as diag_kernel does, each workgroup a contiguous segment of one plane; every double is split
+   into its three 32-bit digits and added as 64-bit integers -- in registers while the lanes of a
+   wave share a word index, by 64-bit LDS atomics otherwise, per workgroup one integer atomic per
+   non-zero word into its plane's record -- and means_total_kernel adds the planes' records word
+   by word.  No floating-point add and no compare-and-swap anywhere, so the result depends on
+   neither the grid nor the order of arrival; the accumulators are zeroed on the stream by every
+   call.  total (and per_plane: optional, n3 records, one per interior plane) arrive through pinned
+   host memory under the slab's bounded wait, as pft_slab_diag's record; a poisoned slab refuses
+   in the same way.  opts = NULL: thresholds 0.5.  PFT_DIAG_WGS caps the workgroups here too.
+   -2: bad arguments, or more than 2^31 - 1 cells. */
+int pft_slab_means(pft_slab * s, int buf, const pft_diag_opts * opts, pft_means * total, pft_means * per_plane);
+/* HIP-event timing of that kernel pair (scripts/means_time.py), as pft_slab_diag_timing */
+int pft_slab_means_timing(pft_slab * s, int on);
+int pft_slab_means_last_ms(pft_slab * s, double * ms);
 
 /* One Merson stage (stage 1..5) as ONE fused kernel: K = f(stage input) and the pointwise stage
    combine of RK_MPI_SAsolver_hybrid2.c:378-450 (stage 5: error norm :507-524 and the candidate

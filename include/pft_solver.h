@@ -47,6 +47,16 @@ int pft_solver_download(RK_MPI_S_SOLUTION * system);
    PFT_SOLVE_DEVICE_ERROR (below). */
 int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * local, long long * ice_per_plane);
 
+/* f6: the exact sums (pft_means.h) of the device-resident x, under the rules of pft_solver_diag:
+   valid after any fused solve or device IC, -3 without a resident state (never stale numbers), 0
+   from a Service_Callback on one rank and -2 there with several.  global: the whole grid's
+   record, the same words on every rank; local (optional): this slab's; per_plane (optional, this
+   slab's n3 records): one record per plane, global rows first_row + k.  Collective on several
+   ranks: each rank reduces its slab (pft_slab_means) and its 2 144-byte record travels with its
+   status in as many pft_comm_allgather rounds of at most 256 bytes as that takes (9); the records
+   are merged in rank order, every rank returns the same code. */
+int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means * local, pft_means * per_plane);
+
 /* f1 (after RK_MPI_SA_init): the default Params' initial condition (Params:9-21,
    intertrack.c:1880-2010) and, with with_beads, the glass beads (PrecalculateData,
    equation.c:459-530) computed on the device straight into the solver's state, bit for bit what

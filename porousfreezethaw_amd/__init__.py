@@ -103,6 +103,51 @@ class pft_diag(C.Structure):
         return d
 
 
+PFT_XSUM_WORDS = 66
+MEAN_KEYS = ("u", "p", "ice_u", "pore_p")     # include/pft_means.h: PFT_MEAN_U, _P, _U_ICE, _P_PORE
+
+
+class pft_xsum(C.Structure):
+    """include/pft_means.h: value = sum_j w[j] * 2^(32 j - 1074), exactly"""
+    _fields_ = [("w", C.c_longlong * PFT_XSUM_WORDS)]
+
+    def as_int(self):
+        """the exact sum in units of 2^-1074, a Python integer"""
+        return sum(int(w) << (32 * j) for j, w in enumerate(self.w))
+
+
+class pft_means(C.Structure):
+    """include/pft_means.h: per quantity the count of the cells that entered and their exact sum"""
+    _fields_ = [("n", C.c_longlong * len(MEAN_KEYS)), ("sum", pft_xsum * len(MEAN_KEYS))]
+
+    def words(self):
+        """the raw words, counts first: equal lists <=> equal records"""
+        return list(self.n) + [int(w) for s in self.sum for w in s.w]
+
+    def values(self, q):
+        """(n, correctly rounded sum, correctly rounded mean) of quantity q; the mean is the exact
+        quotient sum / n rounded once (CPython's integer true division is correctly rounded), NaN
+        when no cell entered"""
+        n, total = int(self.n[q]), self.sum[q].as_int()
+        out = C.c_double()
+        rc = lib().pft_xsum_round(C.byref(self.sum[q]), C.byref(out))
+        if rc:
+            raise RuntimeError(f"pft_xsum_round failed ({rc})")
+        if n == 0:
+            return 0, out.value, float("nan")
+        try:
+            mean = total / (n << 1074)
+        except OverflowError:     # past DBL_MAX: only a sum that itself rounds to +-Inf can
+            mean = float("inf") if total > 0 else float("-inf")
+        return n, out.value, mean
+
+    def as_dict(self):
+        d = {}
+        for q, k in enumerate(MEAN_KEYS):
+            d[k + "_n"], d[k + "_sum"], d[k + "_mean"] = self.values(q)
+        return d
+
+
 _lib = None
 
 
@@ -189,6 +234,16 @@ def lib():
         L.pft_slab_diag_timing.argtypes = [C.c_void_p, C.c_int]
         L.pft_slab_diag_last_ms.argtypes = [C.c_void_p, dp]
         L.pft_solver_diag.argtypes = [op, dgp, dgp, llp]
+        xp, mp = C.POINTER(pft_xsum), C.POINTER(pft_means)
+        L.pft_xsum_add.argtypes = [xp, C.c_double]
+        L.pft_xsum_combine.argtypes = [xp, xp]
+        L.pft_xsum_round.argtypes = [xp, dp]
+        L.pft_means_host.argtypes = [gp, dp, op, mp, mp]
+        L.pft_means_combine.argtypes = [mp, mp]
+        L.pft_slab_means.argtypes = [C.c_void_p, C.c_int, op, mp, mp]
+        L.pft_slab_means_timing.argtypes = [C.c_void_p, C.c_int]
+        L.pft_slab_means_last_ms.argtypes = [C.c_void_p, dp]
+        L.pft_solver_means.argtypes = [op, mp, mp, mp]
         L.pft_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.pft_comm_size.argtypes = [C.c_void_p]
         _lib = L
@@ -478,15 +533,88 @@ class Simulation:
             d["local"] = mine.as_dict()
         return d
 
+    # -- f6: exact means and z-profiles ----------------------------------------------------------
+    def _means_host_global(self, o, planes):
+        """pft_means_host of self.x, merged over the communicator's ranks in rank order (collective;
+        the record travels in pft_comm_allgather rounds of at most 256 bytes)"""
+        L_ = self.lib
+        mine = pft_means()
+        rc = L_.pft_means_host(C.byref(self.grid), _dp(self.x), C.byref(o), C.byref(mine), planes)
+        if rc:
+            raise RuntimeError(f"pft_means_host failed ({rc})")
+        comm = L_.pft_comm_current()
+        n = L_.pft_comm_size(comm) if comm else 1
+        if n == 1:
+            return mine, mine
+        raw, size = bytes(mine), C.sizeof(pft_means)
+        parts = [bytearray() for _ in range(n)]
+        for off in range(0, size, 256):
+            piece = raw[off:off + 256]
+            every = C.create_string_buffer(n * len(piece))
+            rc = L_.pft_comm_allgather(comm, piece, len(piece), every)
+            if rc:
+                raise RuntimeError(f"pft_comm_allgather failed ({rc})")
+            for r in range(n):
+                parts[r] += every.raw[r * len(piece):(r + 1) * len(piece)]
+        glob = pft_means.from_buffer_copy(bytes(parts[0]))
+        for r in range(1, n):
+            L_.pft_means_combine(C.byref(glob), C.byref(pft_means.from_buffer_copy(bytes(parts[r]))))
+        return glob, mine
+
+    def means(self, p_thr=0.5, gl_thr=0.5, where="device", per_plane=False):
+        """The exact means (include/pft_means.h) of the whole grid as a dict: for u (all cells), p
+        (all cells), ice_u (u where p > p_thr) and pore_p (p where gl < gl_thr) the count *_n of
+        the cells that entered, *_sum, the exact sum rounded once, and *_mean, the exact quotient
+        rounded once (NaN when *_n is 0) -- the same bits on any decomposition.  where="device":
+        of the device-resident state, by pft_solver_means -- no download; collective on several
+        ranks; RuntimeError when nothing is resident.  where="host": pft_means_host of self.x,
+        merged over the ranks (collective too).  per_plane: also u_profile, p_profile,
+        ice_u_profile and pore_p_profile, the means of each of this rank's planes (global rows
+        first_row + k), first_row, "local", this slab's own scalars, and "record" /
+        "plane_records", the raw pft_means structs."""
+        if where not in ("device", "host"):
+            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
+        d = self._means(p_thr, gl_thr, where, per_plane)
+        if d is None:
+            raise RuntimeError("means: no state is resident on the device (no initialised solver, or no "
+                               "fused solve or device IC yet); solve first, or use where='host'")
+        return d
+
+    def _means(self, p_thr, gl_thr, where, per_plane):
+        """means(); None when where="device" and nothing is resident (pft_solver_means' -3, the
+        same on every rank)"""
+        o = pft_diag_opts(p_thr, gl_thr)
+        planes = (pft_means * self.grid.n3)() if per_plane else None
+        if where == "host":
+            glob, mine = self._means_host_global(o, planes)
+        else:
+            glob, mine = pft_means(), pft_means()
+            rc = self.lib.pft_solver_means(C.byref(o), C.byref(glob), C.byref(mine), planes)
+            if rc == -3:
+                return None
+            if rc:
+                raise RuntimeError(f"pft_solver_means failed ({rc}): {self.lib.pft_hip_last_error()}")
+        d = glob.as_dict()
+        if per_plane:
+            for q, k in enumerate(MEAN_KEYS):
+                d[k + "_profile"] = np.array([m.values(q)[2] for m in planes], dtype=np.float64)
+            d["first_row"] = self.grid.first_row
+            d["local"] = mine.as_dict()
+            d["record"] = glob
+            d["plane_records"] = planes
+        return d
+
     def run_series(self, final_time=None, saved_files=None, times=None, snapshot_path=None, comment="",
-                   diag=True, opts=None):
+                   diag=True, opts=None, means=False):
         """The driver's snapshot loop (intertrack.c:2265-2283).  Snapshot 0 is the state as it
         stands (no solve); snapshot s solves to series_times(t0, final_time, saved_files)[s], or
         to times[s - 1] when times= lists the solve targets.  The steps run device-resident
         (pft_solve_ex with KEEP_DEVICE | REUSE_DEVICE: nothing crosses PCIe between snapshots; the
         first call uploads unless the IC is already on the device).  Returns one dict per
         snapshot: snapshot, t, h, steps, steps_total, rc (None for snapshot 0) and, with diag,
-        the global diagnostics (opts: a (p_thr, gl_thr) pair).  snapshot_path: every snapshot is
+        the global diagnostics (opts: a (p_thr, gl_thr) pair); with means=True also the scalar
+        keys of means() (u_mean, p_mean, ice_u_mean, pore_p_mean, their _sum and _n), so that
+        write_series_txt(rows, path, key="u_mean") writes a series of them.  snapshot_path: every snapshot is
         also downloaded and written to "<snapshot_path>.%03d.ncd" with the reference's snapshot /
         total_snapshots attributes.  Collective on several ranks.  A solve that returns 1 (a
         Service_Callback break) ends the series with that row."""
@@ -511,6 +639,14 @@ class Simulation:
                 if d is None and s == 0:
                     # snapshot 0 of a host IC: the state is still the host array
                     d = self._diagnostics(p_thr, gl_thr, "host", False)
+                if d is None:
+                    raise RuntimeError("run_series: no state is resident on the device after the solve "
+                                       "(the host-staged path keeps none)")
+                row.update(d)
+            if means:
+                d = self._means(p_thr, gl_thr, "device", False)
+                if d is None and s == 0:
+                    d = self._means(p_thr, gl_thr, "host", False)
                 if d is None:
                     raise RuntimeError("run_series: no state is resident on the device after the solve "
                                        "(the host-staged path keeps none)")

@@ -750,6 +750,64 @@ int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * lo
 	return 0;
 }
 
+int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means * local, pft_means * per_plane)
+{
+	/* f6: the exact sums of the device-resident x, under pft_solver_diag's rules.  A rank's record
+	   and its status are longer than one allgather round carries, so they travel in rounds of at
+	   most 256 bytes; every rank makes every round (a rank that failed locally still takes part)
+	   and merges the records in rank order: integer sums, the same bits on every rank */
+	enum { ROUND = 256 };
+	struct means_msg { long long status; pft_means m; };
+	struct means_msg * all;      /* (loopback ranks are threads of one process: nothing static) */
+	char piece[PFT_DIAG_MAX_RANKS * ROUND];
+	struct means_msg mine;
+	pft_comm * c = comm();
+	const int nprocs = pft_comm_size(c);
+	int rc, r, bad = 0, first_bad = 0;
+	size_t off;
+	if(!global) return -2;
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if(R.in_callback && nprocs > 1) return -2;
+	if(nprocs > PFT_DIAG_MAX_RANKS) return -2;
+	memset(&mine, 0, sizeof mine);
+	rc = pft_slab_means(R.slab, PFT_BUF_X, opts, &mine.m, per_plane);
+	mine.status = rc;
+	if(nprocs == 1) {
+		if(rc) { R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
+		*global = mine.m;
+		if(local) *local = mine.m;
+		return 0;
+	}
+	/* (a failed allocation is this rank's failure, met after the rounds like any other) */
+	all = (struct means_msg *)malloc((size_t)nprocs * sizeof *all);
+	if(!all && !mine.status) mine.status = -1;
+	for(off = 0; off < sizeof mine; off += ROUND) {
+		const int bytes = (int)(sizeof mine - off < ROUND ? sizeof mine - off : ROUND);
+		if((rc = pft_comm_allgather(c, (const char *)&mine + off, bytes, piece))) {
+			free(all);
+			R.last_status = rc;
+			return PFT_SOLVE_DEVICE_ERROR;
+		}
+		if(off == 0)
+			for(r = 0; r < nprocs; r++) {
+				long long st;
+				memcpy(&st, piece + (size_t)r*bytes, sizeof st);
+				if(st) { bad = 1; if(!first_bad) first_bad = (int)st; }
+			}
+		for(r = 0; r < nprocs && all; r++) memcpy((char *)&all[r] + off, piece + (size_t)r*bytes, bytes);
+	}
+	if(bad) {
+		free(all);
+		R.last_status = mine.status ? (int)mine.status : first_bad;
+		return PFT_SOLVE_DEVICE_ERROR;
+	}
+	*global = all[0].m;
+	for(r = 1; r < nprocs; r++) pft_means_combine(global, &all[r].m);
+	if(local) *local = mine.m;
+	free(all);
+	return 0;
+}
+
 /* the common end of the device IC paths: every rank's outcome agreed (a rank that failed locally
    still takes part, so that no other rank is left inside a collective: every rank returns the same,
    most negative, code), then the ghost planes exchanged as at an upload and gl_keep agreed */

@@ -468,15 +468,16 @@ class Case:
         return Simulation(*self.n, self.L, self.calc_mode, self.params, nprocs=nprocs, rank=rank, beads=beads,
                           icond=self.icond_programs(), tau=self.tau, tau_min=self.tau_min, delta=self.delta, **kw)
 
-    def run(self, nprocs=1, rank=0, beads=None, snapshot_path=None, comment="", diag=True, opts=None, **kw):
+    def run(self, nprocs=1, rank=0, beads=None, snapshot_path=None, comment="", diag=True, opts=None,
+            means=False, **kw):
         """the whole case as the driver runs it (intertrack.c:2265-2283): this slab's simulation
         (simulation(); **kw goes to it), then saved_files snapshots up to final_time
-        (Simulation.run_series).  Returns the rows, one per snapshot; write_series_txt() turns them
-        into the published series file."""
+        (Simulation.run_series; means=True: every row also carries the exact means).  Returns the
+        rows, one per snapshot; write_series_txt() turns them into the published series file."""
         sim = self.simulation(nprocs=nprocs, rank=rank, beads=beads, **kw)
         try:
             return sim.run_series(self.final_time, self.saved_files, snapshot_path=snapshot_path, comment=comment,
-                                  diag=diag, opts=opts)
+                                  diag=diag, opts=opts, means=means)
         finally:
             sim.close()
 
