@@ -176,6 +176,36 @@ int pft_slab_means(pft_slab * s, int buf, const pft_diag_opts * opts, pft_means 
 int pft_slab_means_timing(pft_slab * s, int on);
 int pft_slab_means_last_ms(pft_slab * s, double * ms);
 
+/* f7: snapshots from and into the resident state.  The *image* of buffer `buf` is, for q = u, p,
+   gl in turn, this slab's n3*n1*n2 interior doubles as big-endian 8-byte words (image_bytes in
+   all): exactly the bytes the slab owns in each variable of the dataset (pft_io.h), whose host twin
+   is pft_snapshot_image_host.  export_be writes it to dst, device memory or host-mapped pinned
+   memory (8-byte aligned), by one flat streaming kernel on the compute stream, ordered after
+   everything queued there: 16-byte loads and stores, a 64-bit byte swap between them -- a pure bit
+   move, so NaN payloads, -0.0 and subnormals survive -- no LDS, no atomics; no ghost plane is read.
+   import_be is the inverse: it writes the interiors of X and XN from src (device-accessible), as the
+   device IC does (ghost planes untouched: the caller exchanges them), and reports in *gl_unclean
+   whether a gl value is -0.0 or NaN (pft_slab_ic_default's contract, for pft_slab_set_gl_keep).
+   Both wait for the kernel with the slab's bounded wait (pft_slab_sync); a poisoned slab refuses
+   as in pft_slab_diag. */
+size_t pft_slab_image_bytes(const pft_slab * s);
+int pft_slab_export_be(pft_slab * s, int buf, void * dst);
+int pft_slab_import_be(pft_slab * s, const void * src, int * gl_unclean);
+/* the slab's image-sized pinned, host-mapped buffer (allocated by the first call, freed by
+   pft_slab_destroy once the background writer of pft_io.h is done with it): its host and device
+   addresses */
+int pft_slab_image(pft_slab * s, void ** host, void ** dev);
+/* the image of `buf` into that buffer, *image its host address, valid when the call returns: the
+   state may change from then on.  link PFT_SNAP_LINK_DIRECT: the kernel stores straight into the
+   host-mapped buffer; PFT_SNAP_LINK_STAGED: into a device staging image, followed by one
+   hipMemcpyAsync on the compute stream.  Waits first until no job of the background writer reads
+   the buffer's previous image, then -- bounded -- for the stream. */
+enum { PFT_SNAP_LINK_DIRECT = 0, PFT_SNAP_LINK_STAGED = 1 };
+int pft_slab_snapshot_export(pft_slab * s, int buf, int link, void ** image);
+/* HIP-event timing of the export kernel alone (scripts/snapshot_time.py), as pft_slab_diag_timing */
+int pft_slab_snapshot_timing(pft_slab * s, int on);
+int pft_slab_snapshot_last_ms(pft_slab * s, double * ms);
+
 /* One Merson stage (stage 1..5) as ONE fused kernel: K = f(stage input) and the pointwise stage
    combine of RK_MPI_SAsolver_hybrid2.c:378-450 (stage 5: error norm :507-524 and the candidate
    update :657-668 into XN).  t_stage: time passed to f (for the Dirichlet value);  coef: h3,

@@ -24,6 +24,8 @@
 #ifndef PFT_IO_H
 #define PFT_IO_H
 
+#include <stddef.h>
+
 #include "pft_model.h"
 
 #ifdef __cplusplus
@@ -54,8 +56,38 @@ int pft_snapshot_write(const char * path, const pft_grid * g, const double * par
 /* dimensions, attributes (info) and, if param != NULL, the model parameters of a dataset */
 int pft_snapshot_read_info(const char * path, int * n1, int * n2, int * total_n3,
                            pft_snapshot_info * info, double * param);
+/* the attributes a continued series starts from (continue_series, intertrack.c:1650-1662):
+   snapshot, total_snapshots, t, final_time, tau; -3 when one of them is missing */
+int pft_snapshot_read_series(const char * path, int * snapshot, int * total_snapshots, double * t,
+                             double * final_time, double * tau);
 /* this slab's interior planes into the host padded array x (ghost cells untouched) */
 int pft_snapshot_read_slab(const char * path, const pft_grid * g, double * x);
+
+/* f7: the image of a slab: for q = u, p, gl in turn its n3*n1*n2 interior doubles as big-endian
+   8-byte words -- exactly the bytes the slab owns in each variable of the dataset.  image_host
+   builds it from the host padded array (the twin of the device's pft_slab_export_be); ranges are
+   the three places of a slab's image in an existing dataset (-4: its dimensions differ from the
+   grid's), write_image / read_image move an image there and back (pwrite / pread of this slab's
+   planes only). */
+typedef struct {
+	unsigned long long off[3];   /* file offset of this slab's planes of u, p, gl */
+	unsigned long long bytes;    /* per variable: 8 * n3 * n1 * n2 */
+} pft_snapshot_ranges;
+size_t pft_snapshot_image_bytes(const pft_grid * g);
+int pft_snapshot_image_host(const pft_grid * g, const double * x_padded, void * out);
+int pft_snapshot_slab_ranges(const char * path, const pft_grid * g, pft_snapshot_ranges * r);
+int pft_snapshot_write_image(const char * path, const pft_snapshot_ranges * r, const void * image);
+int pft_snapshot_read_image(const char * path, const pft_snapshot_ranges * r, void * image);
+/* The background writer: one thread per process, started by the first job, which writes the jobs
+   in the order they were queued.  It calls no HIP function and only reads the image, which must
+   stay unchanged until the job is done: writer_release(image) returns once no queued or running
+   job reads that buffer (before it is overwritten or freed); writer_wait() returns once every job
+   is done, with the first error since the previous wait (-1 and errno kept; 0 none);
+   writer_shutdown() writes what is queued and joins the thread (a later job starts a new one). */
+int pft_snapshot_write_image_async(const char * path, const pft_snapshot_ranges * r, const void * image);
+int pft_snapshot_writer_release(const void * image);
+int pft_snapshot_writer_wait(void);
+int pft_snapshot_writer_shutdown(void);
 
 /* the title the reference writes (:1129, :2405): "Intertrack simulation (%s). Time: %g" */
 int pft_snapshot_title(char * buf, int size, const char * comment, double t);

@@ -11,6 +11,7 @@
 
 #include "RK_MPI_SAsolver.h"
 #include "pft_hip.h"
+#include "pft_io.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -73,6 +74,38 @@ int pft_solver_ic_default_device(int with_beads);
    alike: evaluate on the host), else as pft_solver_ic_default_device; -2 a bad program. */
 int pft_solver_ic_formulas_device(int nprog, const int * qs, const int * lens, const int * ops,
                                   const double * args, int with_beads);
+
+/* f7: a snapshot dataset (pft_io.h) of the device-resident x, without a download.  It follows the
+   validity rules of pft_solver_diag: -3 without an initialised solver or a resident state (never
+   a stale file; nothing is created), -2 from a Service_Callback with several ranks.  Collective:
+   rank 0 writes the header (pft_snapshot_create; the version of PFT_SNAP_VERSION(v) in flags, 0 =
+   automatic), the ranks agree the status in an allreduce, which is also the barrier, every rank
+   exports its slab's image (pft_slab_snapshot_export) and waits, bounded, until it is in pinned host
+   memory; then the image goes to the background writer.  With PFT_SNAP_ASYNC the call returns
+   there -- the image has left the device, so the next solve may overwrite x while the file is
+   written -- otherwise it also waits for the write.  PFT_SNAP_DIRECT / PFT_SNAP_STAGED choose the
+   host link of this call (default: staged, the faster one by a little -- 7.26 against 7.41 ms at
+   200x200x400; env PFT_SNAP_LINK=0/1 = direct / staged for that A/B).  Every rank
+   returns the same code: 0, a pft_io.h code (-1: I/O error) or PFT_SOLVE_DEVICE_ERROR.
+   pft_solver_snapshot_wait (collective) returns once every rank's writes are done, with the agreed
+   first error of the writes since the last wait. */
+#define PFT_SNAP_ASYNC    1
+#define PFT_SNAP_DIRECT   2
+#define PFT_SNAP_STAGED   4
+#define PFT_SNAP_VERSION(v) (((v) & 3) << 8)
+#define PFT_SNAP_LINK_DEFAULT PFT_SNAP_LINK_STAGED
+int pft_solver_snapshot_write(const char * path, const double * param, const pft_snapshot_info * info, int flags);
+int pft_solver_snapshot_wait(void);
+/* f7 (after RK_MPI_SA_init): the state of a snapshot dataset read on the device, as a restart
+   (icond_file, intertrack.c:2023-2117): each rank preads only its own planes -- no distribution
+   through a master -- and imports them into X and XN (pft_slab_import_be); then exactly the end of
+   the device ICs: outcome agreed across ranks, ghost planes exchanged, gl_keep set, the state
+   resident.  system->x is not written (pft_solver_download).  -4 on every rank, before any device
+   work, when the dataset's dimensions differ from the grid's; other codes as pft_io.h and
+   pft_solver_ic_default_device.  pft_solver_ic_beads_device overlays the glass beads on the gl of
+   the resident state, as PrecalculateData does for a state from a file (equation.c:507-530). */
+int pft_solver_snapshot_read(const char * path);
+int pft_solver_ic_beads_device(void);
 
 /* RK_MPI_SA_solve / pft_solve_ex return value added to the reference's codes
    (RK_MPI_SAsolver.h:384-392): a HIP or RCCL failure (out of device memory, a device fault, a

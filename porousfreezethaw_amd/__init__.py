@@ -33,6 +33,8 @@ PFT_OPT_PAIR = 10
 PFT_OPT_GATE = 12
 PFT_OPT_FAIL_RHS = 11
 PFT_SOLVE_DEVICE_ERROR = -7
+PFT_SNAP_ASYNC, PFT_SNAP_DIRECT, PFT_SNAP_STAGED = 1, 2, 4      # include/pft_solver.h
+PFT_BUF_X, PFT_BUF_XN = 0, 1                                     # include/pft_hip.h
 MPI_COMM_WORLD = 0x44000000
 
 # every function of the public headers, for the "library exports its ABI" check
@@ -75,6 +77,11 @@ class pft_snapshot_info(C.Structure):
     _fields_ = [("t", C.c_double), ("tau", C.c_double), ("final_time", C.c_double), ("delta", C.c_double),
                 ("snapshot", C.c_int), ("total_snapshots", C.c_int), ("calc_mode", C.c_int),
                 ("title", C.c_char * 256), ("L1", C.c_double), ("L2", C.c_double), ("L3", C.c_double)]
+
+
+class pft_snapshot_ranges(C.Structure):
+    """include/pft_io.h: where a slab's image lies in a dataset"""
+    _fields_ = [("off", C.c_ulonglong * 3), ("bytes", C.c_ulonglong)]
 
 
 class pft_solver_stats(C.Structure):
@@ -245,6 +252,26 @@ def lib():
         L.pft_slab_means_last_ms.argtypes = [C.c_void_p, dp]
         L.pft_solver_means.argtypes = [op, mp, mp, mp]
         L.pft_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        rp, vpp = C.POINTER(pft_snapshot_ranges), C.POINTER(C.c_void_p)
+        L.pft_snapshot_image_bytes.argtypes = [gp]
+        L.pft_snapshot_image_bytes.restype = C.c_size_t
+        L.pft_snapshot_image_host.argtypes = [gp, dp, C.c_void_p]
+        L.pft_snapshot_slab_ranges.argtypes = [C.c_char_p, gp, rp]
+        L.pft_snapshot_read_series.argtypes = [C.c_char_p, ip, ip, dp, dp, dp]
+        L.pft_snapshot_write_image.argtypes = [C.c_char_p, rp, C.c_void_p]
+        L.pft_snapshot_read_image.argtypes = [C.c_char_p, rp, C.c_void_p]
+        L.pft_snapshot_write_image_async.argtypes = [C.c_char_p, rp, C.c_void_p]
+        L.pft_snapshot_writer_release.argtypes = [C.c_void_p]
+        L.pft_slab_image_bytes.argtypes = [C.c_void_p]
+        L.pft_slab_image_bytes.restype = C.c_size_t
+        L.pft_slab_export_be.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.pft_slab_import_be.argtypes = [C.c_void_p, C.c_void_p, ip]
+        L.pft_slab_image.argtypes = [C.c_void_p, vpp, vpp]
+        L.pft_slab_snapshot_export.argtypes = [C.c_void_p, C.c_int, C.c_int, vpp]
+        L.pft_slab_snapshot_timing.argtypes = [C.c_void_p, C.c_int]
+        L.pft_slab_snapshot_last_ms.argtypes = [C.c_void_p, dp]
+        L.pft_solver_snapshot_write.argtypes = [C.c_char_p, dp, sp, C.c_int]
+        L.pft_solver_snapshot_read.argtypes = [C.c_char_p]
         L.pft_comm_size.argtypes = [C.c_void_p]
         _lib = L
     return _lib
@@ -293,14 +320,18 @@ def params_array(values):
     return np.array([float(values[k]) for k in PARAM_NAMES], dtype=np.float64)
 
 
-def series_times(t0, final_time, saved_files):
-    """the snapshot times of the driver's loop (intertrack.c:2265-2283 with starting_snapshot 0):
-    snapshot 0 is t0 itself, snapshot s is t0 + ((final_time - t0) * s) / (saved_files - 1), in
-    that operation order in double"""
-    t0, final_time, saved_files = float(t0), float(final_time), int(saved_files)
+def series_times(t0, final_time, saved_files, first=0):
+    """the snapshot times of the driver's loop (intertrack.c:2265-2283) from starting snapshot
+    `first` (0, or a continued series': :1650-1662): snapshot `first` is t0 itself, snapshot
+    s > first is t0 + ((final_time - t0) * (s - first)) / (saved_files - 1 - first) (:2271), in
+    that operation order in double; [t0] alone when first is the last snapshot"""
+    t0, final_time, saved_files, first = float(t0), float(final_time), int(saved_files), int(first)
     if saved_files < 1:
         raise ValueError(f"saved_files must be at least 1, not {saved_files}")
-    return [t0] + [t0 + ((final_time - t0) * float(s)) / float(saved_files - 1) for s in range(1, saved_files)]
+    if not 0 <= first < saved_files:
+        raise ValueError(f"first must lie in 0 .. {saved_files - 1}, not {first}")
+    return [t0] + [t0 + ((final_time - t0) * float(s - first)) / float(saved_files - 1 - first)
+                   for s in range(first + 1, saved_files)]
 
 
 def write_series_txt(rows, path, key="ice_fraction"):
@@ -331,9 +362,13 @@ class Simulation:
     def __init__(self, n1, n2, total_n3, L, calc_mode, params, nprocs=1, rank=0, beads=None,
                  initial=None, tau=1.0, tau_min=0.0, delta=1e-3, t0=0.0, gl_static=False, kz=None,
                  init_solver=True, tile=None, recompute=True, icond=None, device_ic=False,
-                 delta_mode=DELTA_GLOBAL, chunk_mult=None):
+                 delta_mode=DELTA_GLOBAL, chunk_mult=None, icond_file=None):
         if delta_mode not in (DELTA_LOCAL, DELTA_GLOBAL):
             raise ValueError(f"delta_mode must be DELTA_LOCAL or DELTA_GLOBAL, not {delta_mode!r}")
+        if icond_file is not None and (initial is not None or icond is not None or device_ic or not init_solver):
+            # checked before any work: the file's state is read on the device of an initialised solver
+            raise ValueError("icond_file reads the initial state from a snapshot dataset on the device: it cannot "
+                             "be combined with initial=, icond=, device_ic or init_solver=False")
         if device_ic and (initial is not None or not init_solver):
             # checked before any host IC work: the device IC overwrites X/XN and the host copy
             raise ValueError("device_ic computes the IC (the default Params', or icond=) on an initialised "
@@ -363,9 +398,11 @@ class Simulation:
             if any(v < 0 for v in ok):
                 raise ValueError(f"pft_ic_device_ok: a bad icond program ({ok})")
             device_ic = all(v == 1 for v in ok)   # one that is not device-exact: all on the host
-        if device_ic:
+        if device_ic or icond_file is not None:
             self.ic_where = "device"
-        if icond is not None and device_ic:
+        if icond_file is not None:
+            pass                # read on the device after RK_MPI_SA_init (below)
+        elif icond is not None and device_ic:
             pass                # the programs run on the device after RK_MPI_SA_init (below)
         elif icond is not None:
             # the parameter file's icond formulas, compiled by frontend.py (intertrack.c:1831-2012)
@@ -401,8 +438,9 @@ class Simulation:
         if beads is not None and initial is None:   # (also after icond formulas)
             b = np.ascontiguousarray(beads, dtype=np.float64)
             L_.pft_model_set_beads(_dp(b), b.shape[0])
-            # device_ic: the beads are overlaid on the device (pft_solver_ic_default_device)
-            L_.pft_model_set_solution(None if device_ic else _dp(self.x))
+            # device_ic: the beads are overlaid on the device (pft_solver_ic_default_device); on a
+            # state from a file likewise (pft_solver_ic_beads_device)
+            L_.pft_model_set_solution(None if device_ic or icond_file is not None else _dp(self.x))
         else:
             L_.pft_model_set_solution(None)
         if L_.PrecalculateData(_dp(self.chunk_mult)):
@@ -439,6 +477,22 @@ class Simulation:
                 rc = L_.pft_solver_ic_default_device(1 if beads is not None else 0)
             if rc:
                 raise RuntimeError(f"pft_solver_ic_default_device failed ({rc}): {L_.pft_hip_last_error()}")
+            if L_.pft_solver_download(C.byref(self.system)):
+                raise RuntimeError("pft_solver_download failed")
+        self._snap_pending = False
+        if icond_file is not None:
+            # f7: the state of a snapshot dataset read on the device, every rank its own planes
+            # (icond_file, intertrack.c:2023-2117); the reference overlays the beads on it too
+            # (equation.c:507-530); the host array receives a copy, as with device_ic
+            rc = L_.pft_solver_snapshot_read(os.fsencode(icond_file))
+            if rc:
+                self.close()
+                raise OSError(f"pft_solver_snapshot_read({icond_file}) failed ({rc}): {L_.pft_hip_last_error()}")
+            if beads is not None:
+                rc = L_.pft_solver_ic_beads_device()
+                if rc:
+                    self.close()
+                    raise RuntimeError(f"pft_solver_ic_beads_device failed ({rc}): {L_.pft_hip_last_error()}")
             if L_.pft_solver_download(C.byref(self.system)):
                 raise RuntimeError("pft_solver_download failed")
 
@@ -604,8 +658,48 @@ class Simulation:
             d["plane_records"] = planes
         return d
 
+    # -- f7: snapshots from the resident state -----------------------------------------------------
+    def snapshot_device(self, path, info, wait=True, version=0, link=None):
+        """Write the device-resident state as the snapshot dataset `path` (info: snapshot_info())
+        without a download: the slab's image is byte-swapped on the device into pinned host memory
+        and written by the library's background thread (pft_solver_snapshot_write; collective on
+        several ranks).  wait=False returns once the image has left the device -- the next solve may
+        run while the file is written; snapshot_wait() (or close()) then ends the write and reports
+        its errors.  version: 0 automatic, 1 CDF-1, 2 CDF-2.  link: None (the default host link),
+        "direct" or "staged".  RuntimeError when nothing is resident (no file is created)."""
+        if link not in (None, "direct", "staged"):
+            raise ValueError(f"link must be None, 'direct' or 'staged', not {link!r}")
+        if version not in (0, 1, 2):
+            raise ValueError(f"version must be 0, 1 or 2, not {version!r}")
+        flags = (0 if wait else PFT_SNAP_ASYNC) | (version << 8)
+        flags |= {None: 0, "direct": PFT_SNAP_DIRECT, "staged": PFT_SNAP_STAGED}[link]
+        if not self._snapshot_device(path, info, flags):
+            raise RuntimeError("snapshot_device: no state is resident on the device (no initialised solver, or "
+                               "no fused solve or device IC yet)")
+
+    def _snapshot_device(self, path, info, flags):
+        """snapshot_device(); False when nothing is resident (pft_solver_snapshot_write's -3, the same
+        on every rank, and no file)"""
+        rc = self.lib.pft_solver_snapshot_write(os.fsencode(path), _dp(self.params), C.byref(info), flags)
+        if rc == -3:
+            return False
+        if rc:
+            raise OSError(f"pft_solver_snapshot_write({path}) failed ({rc}): {self.lib.pft_hip_last_error()}")
+        if flags & PFT_SNAP_ASYNC:
+            self._snap_pending = True
+        return True
+
+    def snapshot_wait(self):
+        """wait for the background writes of snapshot_device(wait=False); OSError for the first one
+        that failed (collective on several ranks)"""
+        self._snap_pending = False
+        rc = self.lib.pft_solver_snapshot_wait()
+        if rc:
+            raise OSError(f"pft_solver_snapshot_wait: a background snapshot write failed ({rc})")
+
     def run_series(self, final_time=None, saved_files=None, times=None, snapshot_path=None, comment="",
-                   diag=True, opts=None, means=False):
+                   diag=True, opts=None, means=False, snapshot_where="host", snapshot_async=False,
+                   first_snapshot=0, total_snapshots=None, skip_first=False):
         """The driver's snapshot loop (intertrack.c:2265-2283).  Snapshot 0 is the state as it
         stands (no solve); snapshot s solves to series_times(t0, final_time, saved_files)[s], or
         to times[s - 1] when times= lists the solve targets.  The steps run device-resident
@@ -617,27 +711,53 @@ class Simulation:
         write_series_txt(rows, path, key="u_mean") writes a series of them.  snapshot_path: every snapshot is
         also downloaded and written to "<snapshot_path>.%03d.ncd" with the reference's snapshot /
         total_snapshots attributes.  Collective on several ranks.  A solve that returns 1 (a
-        Service_Callback break) ends the series with that row."""
+        Service_Callback break) ends the series with that row.
+        snapshot_where="device": the files come from snapshot_device() -- no download; with
+        snapshot_async each write overlaps the next interval's steps and the series ends with
+        snapshot_wait().  first_snapshot=k continues a series (continue_series,
+        intertrack.c:1642-1669, 2265-2271): the state as it stands is snapshot k of saved_files,
+        rows and file names are numbered from k and the targets are series_times(..., first=k);
+        snapshot k is written again unless skip_first (:2315).  total_snapshots: the files'
+        attribute when times= is given (default: first_snapshot + the number of rows)."""
+        if snapshot_where not in ("host", "device"):
+            raise ValueError(f"snapshot_where must be 'host' or 'device', not {snapshot_where!r}")
+        if snapshot_async and snapshot_where != "device":
+            raise ValueError("snapshot_async needs snapshot_where='device'")
+        first = int(first_snapshot)
+        if first < 0:
+            raise ValueError(f"first_snapshot must not be negative, not {first_snapshot}")
         t0 = self.system.t
         if times is not None:
             targets = [t0] + [float(t) for t in times]
         else:
             if final_time is None or saved_files is None:
                 raise ValueError("run_series needs final_time and saved_files, or times=")
-            targets = series_times(t0, final_time, saved_files)
+            targets = series_times(t0, final_time, saved_files, first)
+        total = first + len(targets) if total_snapshots is None else int(total_snapshots)
         p_thr, gl_thr = opts if opts is not None else (0.5, 0.5)
         end = targets[-1] if final_time is None else float(final_time)
         rows = []
-        for s, T in enumerate(targets):
+        try:
+            rows = self._run_series(targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
+                                    snapshot_where, snapshot_async, skip_first)
+        finally:
+            if self._snap_pending:
+                self.snapshot_wait()
+        return rows
+
+    def _run_series(self, targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
+                    snapshot_where, snapshot_async, skip_first):
+        rows = []
+        for s, T in enumerate(targets, first):
             rc = None
-            if s > 0:
+            if s > first:
                 rc = self.solve_ex(T, 0, PFT_SOLVE_KEEP_DEVICE | PFT_SOLVE_REUSE_DEVICE)
             row = {"snapshot": s, "t": self.system.t, "h": self.system.h, "steps": self.system.steps,
                    "steps_total": self.system.steps_total, "rc": rc}
             if diag:
                 d = self._diagnostics(p_thr, gl_thr, "device", False)
-                if d is None and s == 0:
-                    # snapshot 0 of a host IC: the state is still the host array
+                if d is None and s == first:
+                    # the first snapshot of a host IC: the state is still the host array
                     d = self._diagnostics(p_thr, gl_thr, "host", False)
                 if d is None:
                     raise RuntimeError("run_series: no state is resident on the device after the solve "
@@ -645,19 +765,28 @@ class Simulation:
                 row.update(d)
             if means:
                 d = self._means(p_thr, gl_thr, "device", False)
-                if d is None and s == 0:
+                if d is None and s == first:
                     d = self._means(p_thr, gl_thr, "host", False)
                 if d is None:
                     raise RuntimeError("run_series: no state is resident on the device after the solve "
                                        "(the host-staged path keeps none)")
                 row.update(d)
-            if snapshot_path is not None:
-                drc = self.lib.pft_solver_download(C.byref(self.system))
-                if drc and not (drc == -2 and s == 0):   # -2 at snapshot 0: a host IC, nothing resident yet
-                    raise RuntimeError(f"pft_solver_download failed ({drc})")
+            if snapshot_path is not None and not (s == first and skip_first):
                 info = snapshot_info(self.system.t, self.system.h, end, self.system.delta, self.grid.calc_mode,
-                                     snapshot=s, total_snapshots=len(targets), comment=comment)
-                save_snapshot(self, "%s.%03d.ncd" % (snapshot_path, s), info)
+                                     snapshot=s, total_snapshots=total, comment=comment)
+                name = "%s.%03d.ncd" % (snapshot_path, s)
+                written = False
+                if snapshot_where == "device":
+                    written = self._snapshot_device(name, info, PFT_SNAP_ASYNC if snapshot_async else 0)
+                    if not written and s != first:
+                        raise RuntimeError("run_series: no state is resident on the device after the solve "
+                                           "(the host-staged path keeps none)")
+                if not written:
+                    # the host path; with "device" the first snapshot of a host IC, not yet resident
+                    drc = self.lib.pft_solver_download(C.byref(self.system))
+                    if drc and not (drc == -2 and s == first):   # -2 at the first: a host IC, nothing resident yet
+                        raise RuntimeError(f"pft_solver_download failed ({drc})")
+                    save_snapshot(self, name, info)
             rows.append(row)
             if rc == 1:
                 break
@@ -690,6 +819,10 @@ class Simulation:
         return self.system.h
 
     def close(self):
+        if getattr(self, "_snap_pending", False):
+            # the background writer still reads the slab's pinned image
+            self._snap_pending = False
+            self.lib.pft_solver_snapshot_wait()
         if self.initialised:
             self.lib.RK_MPI_SA_cleanup()
             self.initialised = False
@@ -720,6 +853,16 @@ def read_snapshot_info(path):
     if rc:
         raise OSError(f"pft_snapshot_read_info({path}) failed ({rc})")
     return n1.value, n2.value, n3.value, info, prm
+
+
+def read_snapshot_series(path):
+    """(rc, snapshot, total_snapshots, t, final_time, tau): the attributes a continued series starts
+    from (pft_snapshot_read_series); rc -3 when one of them is missing, other codes as pft_io.h"""
+    snap, total = C.c_int(), C.c_int()
+    t, final, tau = C.c_double(), C.c_double(), C.c_double()
+    rc = lib().pft_snapshot_read_series(os.fsencode(path), C.byref(snap), C.byref(total), C.byref(t),
+                                        C.byref(final), C.byref(tau))
+    return rc, snap.value, total.value, t.value, final.value, tau.value
 
 
 def load_snapshot(sim, path):

@@ -10,6 +10,7 @@
 #define _XOPEN_SOURCE 700
 #include <errno.h>
 #include <fcntl.h>
+#include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -227,7 +228,9 @@ typedef struct {
 	pft_snapshot_info info;
 	double param[PFT_PARAM_COUNT];
 	int have_param[PFT_PARAM_COUNT];
+	unsigned have;         /* HAVE_* bits: the series attributes found */
 } parsed_t;
+enum { HAVE_T = 1, HAVE_TAU = 2, HAVE_FINAL = 4, HAVE_SNAPSHOT = 8, HAVE_TOTAL = 16 };
 
 typedef struct { const unsigned char * p; size_t n, at; int err; } rd_t;
 
@@ -293,20 +296,20 @@ static int parse_header(int fd, parsed_t * P)
 				const uint64_t bits = get64(&v);                    /* already host order */
 				double d;
 				memcpy(&d, &bits, 8);
-				if(!strcmp(name, "t")) P->info.t = d;
+				if(!strcmp(name, "t")) { P->info.t = d; P->have |= HAVE_T; }
 				else if(!strcmp(name, "L1")) P->info.L1 = d;
 				else if(!strcmp(name, "L2")) P->info.L2 = d;
 				else if(!strcmp(name, "L3")) P->info.L3 = d;
-				else if(!strcmp(name, "tau")) P->info.tau = d;
-				else if(!strcmp(name, "final_time")) P->info.final_time = d;
+				else if(!strcmp(name, "tau")) { P->info.tau = d; P->have |= HAVE_TAU; }
+				else if(!strcmp(name, "final_time")) { P->info.final_time = d; P->have |= HAVE_FINAL; }
 				else if(!strcmp(name, "delta")) P->info.delta = d;
 				else for(a = 0; a < NPARAM; a++)
 					if(!strcmp(name, param_order[a].name)) { P->param[param_order[a].idx] = d; P->have_param[param_order[a].idx] = 1; }
 			} else if(t == NCT_INT && cnt >= 1) {
 				rd_t v = r;
 				const int i = (int)get32(&v);
-				if(!strcmp(name, "snapshot")) P->info.snapshot = i;
-				else if(!strcmp(name, "total_snapshots")) P->info.total_snapshots = i;
+				if(!strcmp(name, "snapshot")) { P->info.snapshot = i; P->have |= HAVE_SNAPSHOT; }
+				else if(!strcmp(name, "total_snapshots")) { P->info.total_snapshots = i; P->have |= HAVE_TOTAL; }
 				else if(!strcmp(name, "calc_mode")) P->info.calc_mode = i;
 			} else if(t == NCT_CHAR && !strcmp(name, "title")) {
 				size_t c = cnt < sizeof(P->info.title) - 1 ? cnt : sizeof(P->info.title) - 1;
@@ -361,6 +364,22 @@ int pft_snapshot_read_info(const char * path, int * n1, int * n2, int * total_n3
 	if(total_n3) *total_n3 = (int)P.n3;
 	if(info) *info = P.info;
 	if(param) for(q = 0; q < PFT_PARAM_COUNT; q++) if(P.have_param[q]) param[q] = P.param[q];
+	return 0;
+}
+
+int pft_snapshot_read_series(const char * path, int * snapshot, int * total_snapshots, double * t,
+                             double * final_time, double * tau)
+{
+	parsed_t P;
+	int fd, rc;
+	if(!path || !snapshot || !total_snapshots || !t || !final_time || !tau) return -2;
+	if((fd = open(path, O_RDONLY)) < 0) return -1;
+	rc = parse_header(fd, &P);
+	close(fd);
+	if(rc) return rc;
+	if(P.have != (HAVE_T | HAVE_TAU | HAVE_FINAL | HAVE_SNAPSHOT | HAVE_TOTAL)) return -3;
+	*snapshot = P.info.snapshot; *total_snapshots = P.info.total_snapshots;
+	*t = P.info.t; *final_time = P.info.final_time; *tau = P.info.tau;
 	return 0;
 }
 
@@ -424,4 +443,189 @@ int pft_snapshot_write(const char * path, const pft_grid * g, const double * par
 	err = rc ? 1 : 0;
 	pft_comm_allreduce_max_i64(c, &err);
 	return rc ? rc : (err ? -1 : 0);
+}
+
+/* ---------------------------------------------------------------------------------------- */
+/* f7: the slab's image -- for q = u, p, gl in turn its n3*n1*n2 interior doubles as big-endian
+   words, exactly the bytes the slab owns in each variable of the dataset -- and the background
+   writer that puts an image into its three file ranges */
+
+size_t pft_snapshot_image_bytes(const pft_grid * g)
+{
+	return g ? 3 * 8 * (size_t)g->n1 * (size_t)g->n2 * (size_t)g->n3 : 0;
+}
+
+int pft_snapshot_image_host(const pft_grid * g, const double * x, void * out)
+{
+	long q, k, j, i;
+	uint64_t * o = (uint64_t *)out;
+	if(!g || !x || !out) return -2;
+	{
+		const long N1 = g->n1 + 2 * PFT_BCOND_THICKNESS, N2 = g->n2 + 2 * PFT_BCOND_THICKNESS;
+		const long N3 = g->n3 + 2 * PFT_BCOND_THICKNESS, S = N1 * N2 * N3;
+		for(q = 0; q < 3; q++)
+			for(k = 0; k < g->n3; k++)
+				for(j = 0; j < g->n2; j++) {
+					const double * row = x + q * S + ((k + PFT_BCOND_THICKNESS) * N2 + j + PFT_BCOND_THICKNESS) * N1 +
+					                     PFT_BCOND_THICKNESS;
+					for(i = 0; i < g->n1; i++) *o++ = d2be(row[i]);
+				}
+	}
+	return 0;
+}
+
+int pft_snapshot_slab_ranges(const char * path, const pft_grid * g, pft_snapshot_ranges * r)
+{
+	parsed_t P;
+	int fd, rc, q;
+	if(!path || !g || !r) return -2;
+	if((fd = open(path, O_RDONLY)) < 0) return -1;
+	rc = parse_header(fd, &P);
+	close(fd);
+	if(rc) return rc;
+	if(P.n1 != g->n1 || P.n2 != g->n2 || P.n3 != g->total_n3) return -4;
+	r->bytes = 8ULL * (uint64_t)g->n1 * (uint64_t)g->n2 * (uint64_t)g->n3;
+	for(q = 0; q < 3; q++)
+		r->off[q] = P.begin[q] + 8ULL * (uint64_t)g->first_row * (uint64_t)g->n1 * (uint64_t)g->n2;
+	return 0;
+}
+
+static int image_io(const char * path, const pft_snapshot_ranges * r, void * image, int writing)
+{
+	int fd, rc = 0, q, e;
+	if((fd = open(path, writing ? O_WRONLY : O_RDONLY)) < 0) return -1;
+	for(q = 0; q < 3 && !rc; q++) {
+		char * at = (char *)image + (size_t)q * r->bytes;
+		rc = writing ? write_all(fd, at, (size_t)r->bytes, (off_t)r->off[q]) : read_all(fd, at, (size_t)r->bytes, (off_t)r->off[q]);
+	}
+	e = errno;
+	if(close(fd) && !rc) rc = -1; else errno = e;
+	return rc;
+}
+
+int pft_snapshot_write_image(const char * path, const pft_snapshot_ranges * r, const void * image)
+{
+	if(!path || !r || !image) return -2;
+	return image_io(path, r, (void *)image, 1);
+}
+
+int pft_snapshot_read_image(const char * path, const pft_snapshot_ranges * r, void * image)
+{
+	if(!path || !r || !image) return -2;
+	return image_io(path, r, image, 0);
+}
+
+/* One writer thread per process, started by the first job.  Jobs are written in the order they
+   were queued; the thread calls nothing but open/pwrite/close and only reads the image. */
+typedef struct snap_job {
+	struct snap_job * next;
+	char * path;
+	pft_snapshot_ranges r;
+	const void * image;
+} snap_job;
+
+static struct {
+	pthread_mutex_t mu;
+	pthread_cond_t work, done;
+	pthread_t thread;
+	int started, stop;
+	snap_job *head, *tail;       /* queued */
+	snap_job * running;          /* being written */
+	int err, err_errno;          /* the first failure since the last wait */
+} W = { PTHREAD_MUTEX_INITIALIZER, PTHREAD_COND_INITIALIZER, PTHREAD_COND_INITIALIZER };
+
+static void * writer_main(void * arg)
+{
+	(void)arg;
+	pthread_mutex_lock(&W.mu);
+	for(;;) {
+		snap_job * j;
+		int rc, e;
+		while(!W.head && !W.stop) pthread_cond_wait(&W.work, &W.mu);
+		if(!W.head) break;                                          /* stop, and the queue is empty */
+		j = W.head;
+		W.head = j->next;
+		if(!W.head) W.tail = NULL;
+		W.running = j;
+		pthread_mutex_unlock(&W.mu);
+		rc = image_io(j->path, &j->r, (void *)j->image, 1);
+		e = errno;
+		pthread_mutex_lock(&W.mu);
+		if(rc && !W.err) { W.err = rc; W.err_errno = e; }
+		W.running = NULL;
+		free(j->path);
+		free(j);
+		pthread_cond_broadcast(&W.done);
+	}
+	pthread_mutex_unlock(&W.mu);
+	return NULL;
+}
+
+int pft_snapshot_write_image_async(const char * path, const pft_snapshot_ranges * r, const void * image)
+{
+	snap_job * j;
+	if(!path || !r || !image) return -2;
+	if(!(j = (snap_job *)calloc(1, sizeof *j))) return -1;
+	if(!(j->path = strdup(path))) { free(j); return -1; }
+	j->r = *r;
+	j->image = image;
+	pthread_mutex_lock(&W.mu);
+	if(!W.started) {
+		W.stop = 0;
+		if(pthread_create(&W.thread, NULL, writer_main, NULL)) {
+			pthread_mutex_unlock(&W.mu);
+			free(j->path); free(j);
+			return -1;
+		}
+		W.started = 1;
+	}
+	if(W.tail) W.tail->next = j; else W.head = j;
+	W.tail = j;
+	pthread_cond_signal(&W.work);
+	pthread_mutex_unlock(&W.mu);
+	return 0;
+}
+
+static int image_busy(const void * image)
+{
+	const snap_job * j;
+	if(W.running && W.running->image == image) return 1;
+	for(j = W.head; j; j = j->next) if(j->image == image) return 1;
+	return 0;
+}
+
+int pft_snapshot_writer_release(const void * image)
+{
+	pthread_mutex_lock(&W.mu);
+	while(image_busy(image)) pthread_cond_wait(&W.done, &W.mu);
+	pthread_mutex_unlock(&W.mu);
+	return 0;
+}
+
+int pft_snapshot_writer_wait(void)
+{
+	int rc, e;
+	pthread_mutex_lock(&W.mu);
+	while(W.head || W.running) pthread_cond_wait(&W.done, &W.mu);
+	rc = W.err; e = W.err_errno;
+	W.err = 0; W.err_errno = 0;
+	pthread_mutex_unlock(&W.mu);
+	if(rc) errno = e;
+	return rc;
+}
+
+int pft_snapshot_writer_shutdown(void)
+{
+	pthread_t t;
+	pthread_mutex_lock(&W.mu);
+	if(!W.started) { pthread_mutex_unlock(&W.mu); return 0; }
+	W.stop = 1;
+	t = W.thread;
+	pthread_cond_broadcast(&W.work);
+	pthread_mutex_unlock(&W.mu);
+	pthread_join(t, NULL);                                         /* the queued jobs are written first */
+	pthread_mutex_lock(&W.mu);
+	W.started = 0;
+	pthread_mutex_unlock(&W.mu);
+	return 0;
 }

@@ -909,6 +909,105 @@ int pft_solver_ic_formulas_device(int nprog, const int * qs, const int * lens, c
 	return ic_device_finish(ret, unclean);
 }
 
+int pft_solver_ic_beads_device(void)
+{
+	/* the glass beads over the gl already in X and XN (a state read by pft_solver_snapshot_read:
+	   the reference overlays them on a file's state too, equation.c:507-530 -- a max, so idempotent
+	   on the case's own file), ended as every device IC */
+	pft_ic_tables tb;
+	double * store = NULL;
+	int * istore = NULL, unclean = 0, rc, ret = 0;
+	if(R.max_n == 0 || !R.slab || !R.device_valid) return -3;
+	if((rc = pft_model_ic_tables(&tb, 1, &store, &istore))) ret = rc;
+	else if((rc = pft_slab_ic_beads(R.slab, &tb, &unclean))) { R.last_status = rc; ret = PFT_SOLVE_DEVICE_ERROR; }
+	free(store);
+	free(istore);
+	return ic_device_finish(ret, unclean);
+}
+
+/* ---------------------------------------------------------------------------------------- */
+/* f7: snapshots from and into the resident state */
+
+/* the host link of a device snapshot: kept after the measurement of DESIGN.md section 7 f7; env
+   PFT_SNAP_LINK=0/1 (direct / staged) overrides it for that A/B */
+static int snap_link(int flags)
+{
+	const char * e = getenv("PFT_SNAP_LINK");
+	if(flags & PFT_SNAP_STAGED) return PFT_SNAP_LINK_STAGED;
+	if(flags & PFT_SNAP_DIRECT) return PFT_SNAP_LINK_DIRECT;
+	if(e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] - '0';
+	return PFT_SNAP_LINK_DEFAULT;
+}
+
+/* the ranks agree a status: every rank returns the most negative code (0: all well) */
+static int snap_agree(int rc)
+{
+	pft_comm * c = comm();
+	long long v = -(long long)rc;
+	int crc;
+	if(pft_comm_size(c) == 1) return rc;
+	if((crc = pft_comm_allreduce_max_i64(c, &v))) { R.last_status = crc; return PFT_SOLVE_DEVICE_ERROR; }
+	return (int)-v;
+}
+
+int pft_solver_snapshot_write(const char * path, const double * param, const pft_snapshot_info * info, int flags)
+{
+	pft_comm * c = comm();
+	const int nprocs = pft_comm_size(c), version = (flags >> 8) & 3;
+	pft_snapshot_ranges r;
+	void * image = NULL;
+	int rc = 0;
+	if(!path || !param || !info || version > 2) return -2;
+	/* the validity rules of pft_solver_diag: never a stale file */
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if(R.in_callback && nprocs > 1) return -2;
+	/* rank 0 writes the header; the agreed status is also the barrier before the other ranks open
+	   the file */
+	if(R.slab_grid.rank == 0) rc = pft_snapshot_create(path, &R.slab_grid, param, info, version);
+	if((rc = snap_agree(rc))) return rc;
+	rc = pft_snapshot_slab_ranges(path, &R.slab_grid, &r);
+	/* the image leaves the device: when this returns, the next solve may overwrite X */
+	if(!rc && (rc = pft_slab_snapshot_export(R.slab, PFT_BUF_X, snap_link(flags), &image))) {
+		R.last_status = rc;
+		rc = PFT_SOLVE_DEVICE_ERROR;
+	}
+	if(!rc) rc = pft_snapshot_write_image_async(path, &r, image);
+	if(!rc && !(flags & PFT_SNAP_ASYNC)) rc = pft_snapshot_writer_wait();
+	return snap_agree(rc);
+}
+
+int pft_solver_snapshot_wait(void)
+{
+	return snap_agree(pft_snapshot_writer_wait());
+}
+
+int pft_solver_snapshot_read(const char * path)
+{
+	pft_grid g;
+	pft_snapshot_ranges r;
+	void * image = NULL;
+	int rc, ret = 0, unclean = 0;
+	if(!path) return -2;
+	if(R.max_n == 0) return -3;
+	if(pft_model_get_grid(&g)) return -2;
+	/* the header, and with it a dimension mismatch (-4, the same on every rank), before any device
+	   work; every rank returns the agreed code */
+	rc = pft_snapshot_slab_ranges(path, &g, &r);
+	if((rc = snap_agree(rc))) return rc;
+	if((rc = ensure_slab())) { R.last_status = rc; ret = PFT_SOLVE_DEVICE_ERROR; }
+	else if((rc = pft_slab_image(R.slab, &image, NULL))) { R.last_status = rc; ret = PFT_SOLVE_DEVICE_ERROR; }
+	else {
+		/* each rank reads only its own planes, into the slab's pinned image, which the import kernel
+		   reads in place */
+		void * dev = NULL;
+		pft_snapshot_writer_release(image);
+		pft_slab_image(R.slab, NULL, &dev);
+		if((rc = pft_snapshot_read_image(path, &r, image))) ret = rc;
+		else if((rc = pft_slab_import_be(R.slab, dev, &unclean))) { R.last_status = rc; ret = PFT_SOLVE_DEVICE_ERROR; }
+	}
+	return ic_device_finish(ret, unclean);
+}
+
 int pft_solver_eval_rhs(FLOAT t, const FLOAT * w, FLOAT * dw)
 {
 	/* f(t, w, dw) on host arrays: stage w into A0, exchange its boundary planes, K into K1 */

@@ -20,6 +20,7 @@ by libpft (pft_ic_eval, host C, the reference's node coordinates and multi-pass 
 import math
 import os
 import re
+import warnings
 
 import numpy as np
 
@@ -436,11 +437,17 @@ def _substitute(s, env):
 class Case:
     """One parameter file evaluated the way intertrack.c reads it."""
 
-    def __init__(self, ev, icond, settings, order):
+    def __init__(self, ev, icond, settings, order, icond_mode=0):
         self.ev = ev
         self.icond = icond            # {"u": formula, ...}
         self.settings = settings      # `set` options (after $VAR substitution)
         self.defined = order          # variable names in definition order
+        # which of `icond` (0: formulas) and `set icond_file` (1: a snapshot dataset) came last
+        # (intertrack.c:726-738), and the handling modes (:743-755)
+        self.icond_mode = icond_mode
+        self.icond_file = settings.get("icond_file") if icond_mode else None
+        self.continue_series = bool(settings.get("continue_series"))
+        self.skip_icond = bool(settings.get("skip_icond"))
         g = ev.value
         self.L = (g("L1"), g("L2"), g("L3"))                              # intertrack.c:1491-1497
         from . import PARAM_NAMES
@@ -465,19 +472,69 @@ class Case:
         icond formulas evaluated at every node, glass beads (`beads`: the unit-cube centres of
         data/spheres_positions.txt), t = 0, h = tau, h_min = tau_min, delta"""
         from . import Simulation
+        if self.icond_mode:
+            # the state comes from a snapshot dataset (set icond_file, intertrack.c:1584-1640, 2023-2117)
+            kw.setdefault("tau", self.tau)
+            return Simulation(*self.file_dimensions(), self.L, self.calc_mode, self.params, nprocs=nprocs, rank=rank,
+                              beads=beads, icond_file=self.icond_file, tau_min=self.tau_min, delta=self.delta, **kw)
         return Simulation(*self.n, self.L, self.calc_mode, self.params, nprocs=nprocs, rank=rank, beads=beads,
                           icond=self.icond_programs(), tau=self.tau, tau_min=self.tau_min, delta=self.delta, **kw)
 
+    def file_dimensions(self):
+        """(n1, n2, n3) of a case whose state comes from icond_file (intertrack.c:1620-1639): a
+        dimension the parameter file leaves at 0 is taken from the dataset, another value than the
+        dataset's is an error -- before anything touches the device"""
+        from . import read_snapshot_info
+        if not isinstance(self.icond_file, str) or not self.icond_file:
+            raise EvalError("set icond_file needs a path")
+        try:
+            dims = read_snapshot_info(self.icond_file)[:3]
+        except OSError as e:
+            raise EvalError(f"cannot open the initial conditions dataset: {e}") from None
+        out = []
+        for name, mine, stored in zip(("n1", "n2", "n3"), self.n, dims):
+            if mine != stored and mine != 0:
+                raise EvalError(f"icond_file {self.icond_file}: {name} is {stored} in the dataset, but has been "
+                                f"defined as {mine}")
+            out.append(stored)
+        return tuple(out)
+
+    def series_start(self):
+        """(starting snapshot, total_snapshots, t, final_time, tau) of a continued series, from the
+        attributes of icond_file (continue_series, intertrack.c:1642-1662); a missing one is an error"""
+        from . import read_snapshot_series
+        rc, snap, total, t, final, tau = read_snapshot_series(self.icond_file)
+        if rc:
+            raise EvalError(f"icond_file {self.icond_file}: the dataset does not contain the attributes a continued "
+                            f"series needs (snapshot, total_snapshots, t, final_time, tau; code {rc}); remove "
+                            "continue_series")
+        if not 0 <= snap < total:
+            raise EvalError(f"icond_file {self.icond_file}: snapshot {snap} of {total}")
+        return snap, total, t, final, tau
+
     def run(self, nprocs=1, rank=0, beads=None, snapshot_path=None, comment="", diag=True, opts=None,
-            means=False, **kw):
+            means=False, snapshot_where="host", snapshot_async=False, **kw):
         """the whole case as the driver runs it (intertrack.c:2265-2283): this slab's simulation
         (simulation(); **kw goes to it), then saved_files snapshots up to final_time
         (Simulation.run_series; means=True: every row also carries the exact means).  Returns the
-        rows, one per snapshot; write_series_txt() turns them into the published series file."""
+        rows, one per snapshot; write_series_txt() turns them into the published series file.
+        snapshot_where / snapshot_async: run_series' (files from the resident state, written in the
+        background).  With `set icond_file` the state is read from that dataset; with `set
+        continue_series` as well, the series goes on from it (intertrack.c:1642-1669): the starting
+        snapshot, total_snapshots, t, final_time and tau come from its attributes, rows and files
+        are numbered from the starting snapshot, which is written again unless `set skip_icond`."""
+        final_time, saved_files, first, skip_first = self.final_time, self.saved_files, 0, False
+        if self.continue_series and not self.icond_mode:
+            warnings.warn("continue_series is only meaningful when the initial conditions are loaded from file")
+        elif self.continue_series:
+            first, saved_files, t0, final_time, tau = self.series_start()
+            kw.update(t0=t0, tau=tau)
+            skip_first = self.skip_icond
         sim = self.simulation(nprocs=nprocs, rank=rank, beads=beads, **kw)
         try:
-            return sim.run_series(self.final_time, self.saved_files, snapshot_path=snapshot_path, comment=comment,
-                                  diag=diag, opts=opts, means=means)
+            return sim.run_series(final_time, saved_files, snapshot_path=snapshot_path, comment=comment,
+                                  diag=diag, opts=opts, means=means, snapshot_where=snapshot_where,
+                                  snapshot_async=snapshot_async, first_snapshot=first, skip_first=skip_first)
         finally:
             sim.close()
 
@@ -520,7 +577,7 @@ def load_params(path=None, text=None, env=None, overrides=None):
     env = dict(os.environ if env is None else env)
     overrides = dict(overrides or {})
     ev = Evaluator()
-    icond, settings, order = {}, {}, []
+    icond, settings, order, icond_mode = {}, {}, [], 0
     for lineno, line in enumerate(text.splitlines(True), 1):
         s = line.lstrip(" \t\n")
         cmd = re.match(r"[^ \t\n=#]*", s).group(0)
@@ -533,9 +590,12 @@ def load_params(path=None, text=None, env=None, overrides=None):
             if cmd == "icond":
                 for name, val in opts:
                     icond[name] = val
+                    icond_mode = 0              # set_icond_formula, intertrack.c:728
             elif cmd == "set":
                 for name, val in opts:
                     settings[name] = _substitute(val, env) if val is not None else True
+                    if name == "icond_file":
+                        icond_mode = 1          # set_icond_file, :736
             elif cmd == "break":
                 break
             continue
@@ -552,4 +612,4 @@ def load_params(path=None, text=None, env=None, overrides=None):
         ev.define(name, val)
         if name not in order:
             order.append(name)
-    return Case(ev, icond, settings, order)
+    return Case(ev, icond, settings, order, icond_mode)
