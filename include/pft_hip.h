@@ -238,6 +238,11 @@ int pft_slab_set_consts(pft_slab * s, const pft_consts * c);
    bits differ (0 required) */
 int pft_div_alpha_check(double alpha, unsigned long long n_hashed, const unsigned long long * list,
                         unsigned long long n_list, unsigned long long * mismatches);
+/* test entries: calc_mode 2's cosh -- the C library's algorithm restated (csrc/pft_cosh.h) -- on the
+   device (one plain kernel over the n values of x) and the same code compiled for the host;
+   y[i] = cosh(x[i]), bit for bit x86-64 glibc's (2.28 and later, its FMA build of exp) */
+int pft_cosh_eval(const double * x, double * y, unsigned long long n);
+int pft_cosh_host(const double * x, double * y, unsigned long long n);
 int pft_slab_set_eps_mult(pft_slab * s, const double * em3);
 
 /* u_noise field (PrecalculateData, equation.c:450-456), n3*n1*n2 doubles [k][j][i]; NULL clears */

@@ -880,3 +880,24 @@ def rhs(sim, t, state_padded=None):
     fname = "f_generic_model2" if sim.grid.calc_mode == 2 else "f_generic_model01"
     getattr(L_, fname)(t, _dp(w), _dp(dw))
     return dw, w
+
+
+def _cosh_call(name, x):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.empty_like(x)
+    fn = getattr(lib(), name)
+    fn.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_ulonglong]
+    rc = fn(_dp(x.reshape(-1)), _dp(y.reshape(-1)), x.size)
+    if rc:
+        raise RuntimeError(f"{name} failed ({rc}): {lib().pft_hip_last_error().decode()}")
+    return y
+
+
+def cosh_device(x):
+    """calc_mode 2's cosh (csrc/pft_cosh.h) of every element of x, evaluated on the GPU"""
+    return _cosh_call("pft_cosh_eval", x)
+
+
+def cosh_host(x):
+    """the same code compiled for the host: bit for bit cosh_device and x86-64 glibc's cosh"""
+    return _cosh_call("pft_cosh_host", x)

@@ -6,7 +6,8 @@
 // (hybrid2.c:378-450), the error norm (:507-524) and the candidate update (:657-668).  Every
 // floating-point operation is the reference's, in the reference's order, with contraction
 // disabled (-ffp-contract=off and the pragma below), so results are bit-identical to the CPU
-// reference for calc_mode 0/1/10/11 (mode 2 differs only through device cosh, <= 1 ulp).
+// reference for every calc_mode (mode 2's cosh is the C library's algorithm restated, pft_cosh.h:
+// x86-64 glibc 2.28 and later with its FMA build of exp, which produced the golden vectors).
 //
 // Memory: per slab, a field is (n3+2) planes of n1*n2 doubles (one ghost plane each side, filled
 // only at slab interfaces) between two far ghost planes (the pair kernels' two-plane halo).  Mirror / Dirichlet walls (equation.c:113-263) are folded into the
@@ -31,6 +32,7 @@
 #include "../../include/pft_frontend.h"
 #include "../../include/pft_hip.h"
 #include "../../include/pft_io.h"
+#include "pft_cosh.h"
 #include "pft_ic_ops.h"
 #include "pft_tanh.h"
 
@@ -148,6 +150,14 @@ __global__ __launch_bounds__(256) void div_alpha_check_kernel(pft_consts c, unsi
   if (__double_as_longlong(got) != __double_as_longlong(ref)) atomicAdd(bad, 1ULL);
 }
 
+// test entry (pft_cosh_eval): y[i] = pft_cosh(x[i]), mode 2's cosh on its own
+__global__ __launch_bounds__(256) void cosh_eval_kernel(const double* __restrict__ x, double* __restrict__ y,
+                                                        unsigned long long n)
+{
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = pft_cosh(x[i]);
+}
+
 // K (du, dp) at one cell; dgl is identically 0 (equation.c:731,874)
 template <int MODE>
 __device__ __forceinline__ void rhs_cell(const pft_consts& c, const Col& u, const Col& p, const Col& g,
@@ -174,7 +184,7 @@ __device__ __forceinline__ void rhs_cell(const pft_consts& c, const Col& u, cons
            c.h3_2 * (-lzm * (-u.zm + uc) + lzp * (-uc + u.zp));
   }
   if (MODE == 2) {
-    const double ch = cosh(c.gamma * (uc - c.u_star));
+    const double ch = pft_cosh(c.gamma * (uc - c.u_star));
     const double dpdu = (c.mhg / (ch * ch)) * wi;
     const double d = flux / (rho * (cp - c.L * dpdu));
     du = d;
@@ -243,7 +253,7 @@ __device__ __forceinline__ void rhs_cell_f(const pft_consts& c, const Col& u, co
            c.h3_2 * (-fzm.prod + fzp.prod);
   }
   if (MODE == 2) {
-    const double ch = cosh(c.gamma * (uc - c.u_star));
+    const double ch = pft_cosh(c.gamma * (uc - c.u_star));
     const double dpdu = (c.mhg / (ch * ch)) * wi;
     const double d = flux / (rho * (cp - c.L * dpdu));
     du = d;
@@ -4270,6 +4280,26 @@ int pft_div_alpha_check(double alpha, unsigned long long n_hashed, const unsigne
   if (dl) (void)hipFree(dl);
   if (db) (void)hipFree(db);
   if (e != hipSuccess) return fail(e, "pft_div_alpha_check");
+  return 0;
+}
+
+int pft_cosh_eval(const double* x, double* y, unsigned long long n)
+{
+  if (n > (1ULL << 31) || (n && (!x || !y))) return -2;
+  if (!n) return 0;
+  double *dx = nullptr, *dy = nullptr;
+  const size_t bytes = sizeof(double) * (size_t)n;
+  hipError_t e = hipMalloc((void**)&dx, bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&dy, bytes);
+  if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    cosh_eval_kernel<<<(unsigned)((n + 255) / 256), 256>>>(dx, dy, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(y, dy, bytes, hipMemcpyDeviceToHost);
+  if (dx) (void)hipFree(dx);
+  if (dy) (void)hipFree(dy);
+  if (e != hipSuccess) return fail(e, "pft_cosh_eval");
   return 0;
 }
 
