@@ -1632,10 +1632,23 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
     __syncthreads();
   }
 
-  // one z-step: stage A at plane mm, stage B at plane mm - 1; false after the chunk's last one
-  auto step = [&](auto ph, int mm, PairRaw& rc, PairRaw& rn, PairRaw& rnn) -> bool {
+  // one z-step: stage A at plane mm, stage B at plane mm - 1; false after the chunk's last one.
+  // st 0: any plane of the chunk (every test on the chunk position at run time).  st 1: a
+  // steady-state plane, kb + 2 <= mm <= mlast - 2 (the range is derived at the z-loop below), of a
+  // launch without u_noise (a.noise null, as in every run with u_noise_amp == 0): each of those
+  // tests is decided and compiled out, so the phases are straight-line code but for the per-lane
+  // predicates isA, isB and is_x.  The arithmetic is the same text.
+  auto step = [&](auto ph, auto st, int mm, PairRaw& rc, PairRaw& rn, PairRaw& rnn) -> bool {
     constexpr int PH = decltype(ph)::value;
+    constexpr int ST = decltype(st)::value;
+    constexpr bool SDY = ST != 0;
     constexpr int sA = PH, sAm = (PH + 2) % 3, sAp = (PH + 1) % 3;   // ring slots of planes mm, mm-1, mm+1
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (the steady loop's plane index is laundered like the kernarg pointer: seen as an induction
+    // variable, the plane offsets became a running per-lane offset and six products kept across
+    // the loop, and pair 4+5 spilled the VGPRs the general steps need around the loop)
+    if (SDY) asm volatile("" : "+s"(mm));
+#endif
     {
       PFT_PAIR_BIND(A0, C0);
       (void)C0;
@@ -1646,7 +1659,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       // lands in the ring slot of plane mm - 2, which nobody reads any more -- so that no branch
       // separates a load from its use: with the loads under a branch the compiler's s_waitcnt
       // placement lost track of them and stage A waited for the look-ahead it had just issued.
-      if (mm + 1 <= mlast) {
+      if (SDY || mm + 1 <= mlast) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           const dbl2 v = pair_in_A<SA, GLX>(A0, q, rn);
@@ -1667,11 +1680,11 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       // wave holds no stage-B position (pair_pos), so its SIMD has the wave-phase to spare.
       if constexpr (LWP == 22) {
         if (is_x(A0)) {
-          if (mm + 1 <= mlast) xstore(A0, sAp, rc);
-          if (mm + 2 <= mlast) xload(A0, mm + 2, rn);
+          if (SDY || mm + 1 <= mlast) xstore(A0, sAp, rc);
+          if (SDY || mm + 2 <= mlast) xload(A0, mm + 2, rn);
         }
       }
-      if (mm + 2 <= mlast) pair_load<SA>(A0, pbo(mm + 2), rnn);          // look-ahead
+      if (SDY || mm + 2 <= mlast) pair_load<SA>(A0, pbo(mm + 2), rnn);   // look-ahead
     }
     const int kB = mm - 1;                                   // stage B's plane
     PairRaw ro;
@@ -1685,9 +1698,9 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       else __builtin_amdgcn_s_setprio(0);
       dbl2 (&ka)[2] = KA[PH];
       ka[0] = ka[1] = zero2;
-      if (mm <= mA1 && isA) {
+      if ((SDY || mm <= mA1) && isA) {
         // stage A at plane mm, evaluated as the acting pair's thread does
-        if (mm == n3 - 1 && whi) {
+        if (!SDY && mm == n3 - 1 && whi) {
           // top wall: the ring slot of plane n3 holds the ghost values -- Dirichlet u (equation.c:
           // 175-183), p and gl mirrored -- at this position (its own z neighbour only)
 #pragma unroll
@@ -1707,7 +1720,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
           zp[q] = ZREG ? IA[sAp][q] : LD::ld(lA[sAp][q], posA);
         }
         double du[2], dp[2];
-        const double* nz = A1.noise ? A1.noise + (long)mm * A1.plane + (long)apo : nullptr;
+        const double* nz = SDY ? nullptr : A1.noise ? A1.noise + (long)mm * A1.plane + (long)apo : nullptr;
         pair_rhs<MODE, LWP>(C1, lA[sA][0], lA[sA][1], lA[sA][2], actA, xmcA, xpcA, zm, zc, zp, nz, fzA, du, dp);
         ka[0] = dbl2{du[0], du[1]};
         ka[1] = dbl2{dp[0], dp[1]};
@@ -1715,7 +1728,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         for (int q = 0; q < NBQ; ++q) {
           const dbl2 ib = pair_in_B<SA, GLX>(A1, q, rc, q < 2 ? ka[q < 2 ? q : 0] : zero2);
           LD::st(lB[sA][q], posB, ib);
-          if (mm == 0 && wlo) LD::st(lB[sAm][q], posB, ib);   // bottom wall: plane -1 mirrors plane 0
+          if (!SDY && mm == 0 && wlo) LD::st(lB[sAm][q], posB, ib);   // bottom wall: plane -1 mirrors plane 0
         }
       }
     }
@@ -1735,7 +1748,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       if (OPL) {
         // plane kB's operands from lO, then plane mm's into the same slot (this thread's own; LDS
         // accesses of a wave stay in order)
-        if (kB >= kb && isB) {
+        if ((SDY || kB >= kb) && isB) {
           ro.x[0] = lO[0][ob];
           ro.x[1] = lO[1][ob];
           ro.k1[0] = lO[2][ob];
@@ -1743,7 +1756,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
           ro.k3[0] = lO[4][ob];
           ro.k3[1] = lO[5][ob];
         }
-        if (isB && mm >= kb && mm < ke) {
+        if (isB && (SDY || (mm >= kb && mm < ke))) {
           lO[0][ob] = rc.x[0];
           lO[1][ob] = rc.x[1];
           lO[2][ob] = rc.k1[0];
@@ -1751,13 +1764,13 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
           lO[4][ob] = rc.k3[0];
           lO[5][ob] = rc.k3[1];
         }
-      } else if (SA == 4 && kB >= kb && isB) {
+      } else if (SA == 4 && (SDY || kB >= kb) && isB) {
         pair_load<SA, !GLX>(A2, pbo(kB), ro);
       }
-      if (kB >= kb && isB) {
+      if ((SDY || kB >= kb) && isB) {
         constexpr int sB = (PH + 2) % 3, sBm = (PH + 1) % 3, sBp = PH;   // slots of planes kB, kB-1, kB+1
         const int lo = posB;
-        if (kB == n3 - 1 && whi) {
+        if (!SDY && kB == n3 - 1 && whi) {
           // top wall: the ghost values of plane n3 at this position (as in stage A above)
 #pragma unroll
           // (GLB: gl's ghost is in lA's slot of plane n3, from stage A's top wall)
@@ -1776,7 +1789,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
           zm[2] = glm;
           zp[2] = ZREG ? IA[sBp][2] : LD::ld(lA[sBp][2], posA);
         }
-        if (kB == kb) {
+        if (!SDY && kB == kb) {
           // the z-face below the chunk's first stage-B plane
 #pragma unroll
           for (int s = 0; s < 2; ++s)
@@ -1784,7 +1797,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         }
         double du[2], dp[2];
         const unsigned e0 = pbo(kB);
-        const double* nz = A2.noise ? A2.noise + (long)kB * A2.plane + (long)apo : nullptr;
+        const double* nz = SDY ? nullptr : A2.noise ? A2.noise + (long)kB * A2.plane + (long)apo : nullptr;
         // (GLB: gl's plane from lA, whose rows start one row earlier: slot lo + LWP there)
         const double* lBgl = GLB ? &lA[sB][2][2 * LWP] : &lB[sB][NBQ - 1][0];
         pair_rhs<MODE, LWP>(C2, lB[sB][0], lB[sB][1], lBgl, lo, xmcB, xpcB, zm, zc, zp, nz, fzB, du, dp);
@@ -1813,16 +1826,45 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         }
       }
     }
-    if (mm == ke) return false;
+    if (!SDY && mm == ke) return false;
     __syncthreads();
     return true;
   };
 
   if (kb < ke) {
+    // The steady range.  A step at plane mm has every chunk-position test of step() decided when
+    //   mm + 2 <= mlast   the look-ahead, the next plane's stage-A input and the extras' pair of
+    //                     them all run; with mlast <= mA1 + 1 and mA1 <= ke this also gives
+    //                     mm <= mA1 - 1 (stage A runs, not on a wall plane: at a top wall
+    //                     mlast = n3 - 1, so mm <= n3 - 3), mm < ke (lO is written, the chunk
+    //                     goes on) and kB = mm - 1 < n3 - 1 (no top wall in stage B);
+    //   mm >= kb + 2      stage B runs on a plane above the chunk's first (kB > kb: fzB is
+    //                     carried, lO holds plane kB), and mm >= 2 is no bottom wall plane.
+    // A triple of steps (the register rotation's period, starting at mA0 + 3j in phase 0) is
+    // steady when its first and last step are: mm >= kb + 2 and mm + 4 <= mlast.  mA0 <= kb, so
+    // the chunk's first triple never is; a two-plane boundary chunk (ke = kb + 2, mlast <= kb + 3)
+    // and every chunk of fewer than five planes has none.  The steady triples are a loop of
+    // their own; where it ends, the general triple takes the chunk's last steps (one to five).
+    // A launch with u_noise has no steady triple: a steady body with the noise loads beside the
+    // one without made every instance spill, so its planes all take
+    // the general body, as before.  So do those of pair 4+5 in calc_mode 0 without GLX (a launch
+    // whose gl holds a -0.0 or a NaN), the one kernel that kept a spilled VGPR with the steady
+    // loop: it stays the single z-loop it was.  The 12-pair pitch keeps the single loop too:
+    // 200^3 (100 x 100 planes) ran 1.6% slower with the steady loop, outside the run-to-run range
+    // (profiles/f9_bench_ab.txt).
+    constexpr bool STEADY = LWP == 22 && !(SA == 4 && MODE == 0 && !GLX);
+    const int msteady = a.noise ? -(1 << 30) : mlast - 4;        // last first plane of a steady triple
     for (int mm = mA0;; mm += 3) {
-      if (!step(pft_ic<0>{}, mm, R[0], R[1], R[2])) break;
-      if (!step(pft_ic<1>{}, mm + 1, R[1], R[2], R[0])) break;
-      if (!step(pft_ic<2>{}, mm + 2, R[2], R[0], R[1])) break;
+      if (STEADY && mm >= kb + 2) {
+        for (; mm <= msteady; mm += 3) {
+          step(pft_ic<0>{}, pft_ic<1>{}, mm, R[0], R[1], R[2]);
+          step(pft_ic<1>{}, pft_ic<1>{}, mm + 1, R[1], R[2], R[0]);
+          step(pft_ic<2>{}, pft_ic<1>{}, mm + 2, R[2], R[0], R[1]);
+        }
+      }
+      if (!step(pft_ic<0>{}, pft_ic<0>{}, mm, R[0], R[1], R[2])) break;
+      if (!step(pft_ic<1>{}, pft_ic<0>{}, mm + 1, R[1], R[2], R[0])) break;
+      if (!step(pft_ic<2>{}, pft_ic<0>{}, mm + 2, R[2], R[0], R[1])) break;
     }
   }
 
@@ -1835,13 +1877,14 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       if (ov > m) m = ov;
     }
     const int anynf = __any(nf);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
+    // (the wave and the lane as in the z-loop: threadIdx.x is not kept across it for these tests)
+    const int w = wid;
+    if (lane() == 0) {
       red[w] = m;
       rnf[w] = anynf;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (wid == 0 && lane() == 0) {
       double bm = red[0];
       int bnf = rnf[0];
       for (int q = 1; q < PFT_PBLOCK / 64; ++q) {
@@ -1865,7 +1908,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
     // copies wait for the count (bnd_trigger_kernel) while the interior workgroups go on
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (wid == 0 && lane() == 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
       __hip_atomic_fetch_add(a.bdone, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

@@ -15,7 +15,7 @@ cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
-    m = re.search(r"remark: +(Function Name|VGPRs|VGPRs Spill|SGPRs Spill|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
+    m = re.search(r"remark: +(Function Name|VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
     if not m:
         continue
     k, v = m.group(1), m.group(2)
@@ -28,5 +28,5 @@ for line in out.splitlines():
 for r in rows:
     if flt.search(r["name"]):
         print(f"{r['name']:48s} vgpr {r.get('VGPRs','?'):>4s} vspill {r.get('VGPRs Spill','?'):>3s} "
-              f"sspill {r.get('SGPRs Spill','?'):>3s} occ {r.get('Occupancy [waves/SIMD]','?'):>2s} "
+              f"sspill {r.get('SGPRs Spill','?'):>3s} scratch {r.get('ScratchSize [bytes/lane]','?'):>3s} occ {r.get('Occupancy [waves/SIMD]','?'):>2s} "
               f"lds {r.get('LDS Size [bytes/block]','?')}")
