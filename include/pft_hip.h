@@ -1,6 +1,6 @@
 /*
  * pft_hip.h -- the thin C-ABI shim between libpft's host C code (rk_solver.c, model.c) and
- * the hand-written HIP kernels for gfx950 (porousfreezethaw_amd/csrc/pft_kernels.hip).
+ * the hand-written HIP kernels for gfx950 (porousfreezethaw_amd/csrc/pft_*.hip; csrc/pft_slab.h lists them).
  *
  * Conventions: extern "C"; every call returns int (0 = OK, negative = HIP error, mirroring the
  * reference's negative codes); streams are explicit (opaque handles); no exceptions cross the

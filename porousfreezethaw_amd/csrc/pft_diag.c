@@ -1,6 +1,6 @@
 /*
  * pft_diag.c -- f5: the ice diagnostics on a host array (include/pft_diag.h): the host-layout twin
- * of the device reduction (diag_kernel, pft_kernels.hip) and a second statement of its semantics,
+ * of the device reduction (diag_kernel, pft_reduce.hip) and a second statement of its semantics,
  * written with plain comparisons where the kernel orders doubles by an integer key.
  *
  * Host C99, OpenMP over the planes like pft_ic_eval.  Every quantity is a count or a maximum, so

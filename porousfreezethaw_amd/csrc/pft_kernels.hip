@@ -18,36 +18,20 @@
 // three fields in registers (2.5-D blocking).  x/y neighbours come from the L1/L2; the linear
 // workgroup id is remapped so that the 8 XCDs each take a contiguous run of tiles (their y
 // neighbours then share the XCD's L2, cdna_hip_programming.md T1).
-#include <hip/hip_runtime.h>
+//
+// The reductions (pft_reduce.hip) and the snapshots (pft_snap.hip) are translation units of their
+// own over pft_slab.h, which holds the slab object and what the files share.
+#include "pft_slab.h"
 
-#include <algorithm>
-#include <type_traits>
-#include <vector>
-#include <sched.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../include/pft_frontend.h"
-#include "../../include/pft_hip.h"
-#include "../../include/pft_io.h"
 #include "pft_cosh.h"
 #include "pft_ic_ops.h"
 #include "pft_tanh.h"
 
 #pragma clang fp contract(off)
 
-#define PFT_BLOCK 256      // threads per workgroup of the cache kernel (merson_stage)
-#define PFT_FBLOCK 256     // ... of the fused stage kernel (merson_fused).  A/B: 512 (25 x 20-pair
-                           // tiles, a third fewer halo loads) measured 3-5% slower at 400^3 -- one
-                           // workgroup per CU where 256 fit two to four
-#define PFT_TRING 8
-#define PFT_PUB_SLOTS 64
+__thread char g_err[256];
 
-static __thread char g_err[256];
-
-static int fail(hipError_t e, const char* what)
+int fail(hipError_t e, const char* what)
 {
   snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
   // the failed call also left e as the thread's "last error": reset it, or the next launch's
@@ -55,11 +39,6 @@ static int fail(hipError_t e, const char* what)
   (void)hipGetLastError();
   return -(int)e - 1000;
 }
-#define HIPCHK(x)                                  \
-  do {                                             \
-    hipError_t e_ = (x);                           \
-    if (e_ != hipSuccess) return fail(e_, #x);     \
-  } while (0)
 
 // ------------------------------------------------------------------------------------------
 // model arithmetic (equation.c:330-421, 650-731, 835-874), operation order preserved
@@ -345,7 +324,6 @@ struct StageArgs {
 };
 
 #define PFT_GATE_SKIP (1ULL << 63)
-#define PFT_GATE_SLOTS 64
 
 // the scalars of a gated launch from the decided (t, h), exactly as rk_solver.c's run_fused and
 // run_stage form them (hybrid2.c:355: h/2.0, h/3.0, h/6.0, h/8.0; the stage times t + h3, t + h2,
@@ -2266,180 +2244,6 @@ __global__ void probe_copy_kernel(double* __restrict__ dst, const double* __rest
 // ------------------------------------------------------------------------------------------
 // slab object + shim
 
-// a z-neighbour's buffers mapped into this process (ipc transport): the put kernel and the fused
-// stage kernels store this slab's boundary planes straight into the neighbour's ghost plane
-struct SlabPeer {
-  int on;                              // 1: a neighbour on this side receives our boundary planes
-  int opened;                          // 1: base[] / sig came from hipIpcOpenMemHandle (close them)
-  double* base[PFT_BUF_COUNT];         // the neighbour's buffers by physical index
-  unsigned long long* sig;             // the neighbour's flag words
-  long fs;                             // its field stride
-  int n3;                              // its interior planes
-  int remote;                          // 1: on another GPU (xGMI)
-  int staged;                          // 1: our planes go to its receive buffer (remote, or PFT_IPC_STAGED)
-  double* rbuf;                        // its receive buffer
-};
-
-struct pft_slab {
-  pft_slab_desc d;
-  pft_consts c;          // (ralpha: slab_div_consts)
-  double da_alpha, da_r; // the alpha it was computed for, and the value
-  int da_valid;
-  long fs;
-  int plane;
-  double* buf[PFT_BUF_COUNT];
-  double* buf0[PFT_BUF_COUNT];   // the allocations by physical index (buf[] is permuted by swaps)
-  int phys[PFT_BUF_COUNT];       // role -> physical index; every rank swaps identically, so a role
-                                 // names the same physical buffer on every slab
-  unsigned long long* sig;       // flag words written by the neighbours: [0] from below, [1] from
-                                 // above (monotonic exchange sequence numbers); [8] put counter
-  double* rbuf;                  // staged receive buffer (uncached, 2 x 12 planes; pft_slab_ipc_export)
-  // copy-engine puts (pft_slab_halo_put_ce): the flags are raised by 8-byte SDMA copies from this
-  // device table of sequence numbers (seq_base + 1 .. seq_base + PFT_SEQTAB), refilled from the
-  // pinned halves seqhost[] when an exchange's number leaves it
-  unsigned long long* seqtab;
-  unsigned long long* seqhost;
-  unsigned long long seq_base;
-  int seq_half, seq_n;
-  hipEvent_t ev_seq[2];  // recorded after each refill's H2D copy from that pinned half: the host
-                         // rewrites a half only once the copy that read it last has run
-  // the flags behind the completed plane copies (pft_slab_halo_put_ce, ce_fence): an event after
-  // each copy stream's planes, waited for by the OTHER copy stream, which raises that side's flag
-  int ce_fence;
-  int gpu_ranks;         // ranks of the communicator on this slab's GPU (ipc attach; 0/1: alone)
-  hipEvent_t ev_planes[2];
-  // boundary launches on their own stream (pft_slab_set_boundary_stream; the copy-engine exchange):
-  // a launch of the boundary planes (PFT_K_BOUNDARY/2) runs on `bnd` beside the interior launch on
-  // the compute stream instead of before it; the exchange waits for ev_bnd, and so does the compute
-  // stream before the next launch (pft_slab_halo_wait).  bnd_mode 1: every boundary launch, 2: the
-  // pair kernels' (run_pair), 3: the pair kernels', with the halo waits on `bnd` (the boundary pipeline)
-  int bnd_mode, bnd_pending, ce_streams;
-  int ce_marked;         // pft_slab_halo_mark recorded ev_order[0] after the launch the next put_ce sends
-  int bnd_split;         // the exchange's boundary launch ran before its interior on the compute stream
-  int wait_streamops;    // A/B: halo waits as hipStreamWaitValue64 (env PFT_WAIT_STREAMOPS=1)
-  hipStream_t bnd;
-  hipEvent_t ev_bnd, ev_pre, ev_copy, ev_side, ev_join;
-  // bnd_mode 4 (inline boundary): the pair kernels' boundary chunks lead their interior launch
-  // (PFT_K_INLINE); its boundary workgroups count themselves in *bdone, and the exchange's copies
-  // wait behind bnd_trigger_kernel for the count bdone_target (inline_pending: not yet sent)
-  unsigned long long* bdone;
-  unsigned long long bdone_target;
-  int inline_pending;
-  int trig_early;        // A/B (PFT_CE_TRIG): 1 the trigger queued with the launch, 0 with the copies
-  int stage_inline;      // A/B (PFT_CE_STAGE_INLINE): stage launches inline too (else boundary first)
-  hipEvent_t ev_trig;
-  int put_role, put_f0, put_f1, put_deep;   // the exchange the last halo_put2 sent (its wait receives it)
-  SlabPeer peer[2];              // [0] the neighbour below, [1] above
-  int drop_puts;                 // fault injection: halo puts and flag raises skipped (PFT_IPC_DROP_PUTS)
-  int ipc_poisoned;              // an ipc wait timed out: the flag words were forced past every
-                                 // sequence number, so no later halo wait would block -- every halo
-                                 // exchange, wait and sync refuses (PFT_ERR_IPC_TIMEOUT) until
-                                 // pft_slab_ipc_close resets the flags (a detach / re-attach);
-                                 // 2: the watched communicator aborted (PFT_ERR_COMM_ABORTED, for good)
-  double* staging;      // host padded layout on the device (for upload/download)
-  long S;                // host padded block (one field)
-  unsigned long long* scratch;  // [0] eps bits, [1] nonfinite flag
-  unsigned long long* host_scratch;  // pinned
-  unsigned long long* host_pub;      // pinned, coherent: written by publish_kernel
-  unsigned long long* host_pub_dev;  // its device address
-  hipStream_t stream, comm;
-  hipStream_t side;      // error-norm read-back while the compute stream runs ahead
-  hipEvent_t ev_order[3];  // stream-order events: [0] compute -> comm, [1] comm -> compute,
-                           // [2] the last boundary launch on the comm stream
-  hipEvent_t ev_eps;     // recorded on the compute stream after the error norm is final
-  int eps_marked;        // 1: publish kernel + event; 2: published by stage 5 itself (pub ring)
-  // in-kernel publication (pft_slab_set_inkernel_publish): ring of 2-word slots in pinned,
-  // coherent host memory, one per stage-5 launch; the host pre-sets a slot to the sentinel and
-  // polls it after the launch
-  int inkernel_pub;
-  unsigned long long* pub_ring;      // host address (PFT_PUB_SLOTS x 2 words)
-  unsigned long long* pub_ring_dev;  // its device address
-  unsigned int* pub_count;           // device: finished workgroups of the publishing launch
-  EpsShard* eps_shards;              // device: the error norm's shards (after pub_count's line)
-  unsigned long long* part;          // device: deferred publication partials (2 words per workgroup)
-  long part_cap;                     // ... their capacity in workgroups
-  int defer_n;                       // workgroups of the armed error-norm launch awaiting reduction
-  int defer_slot;                    // ... and its host slot
-  int split_pub;                     // a split stage 4+5's boundary launch armed it; the interior follows
-  // host-side memos (a small slab is host-bound: ~5 launches of a few us per attempted step)
-  int fgeo_valid, fgeo_wx, fgeo_ty;  // fused_geometry(n1, n2) of this slab
-  double fgeo_eff;
-  long kz_key[16];                   // z-chunk cost model: key (occupancy, tiles, planes) -> kz
-  int kz_val[16];
-  int launch_nwg[6], launch_kz[6], launch_ntile[6];   // the last launch that ended stage 1..5 (pft_slab_launch_geometry)
-  int launch_bnd[6];                 // ... and whether it was the boundary launch of a split stage
-  int launch_part;                   // ... and whether the last error-norm launch stored deferred partials
-  long pub_next;                     // slots used so far
-  int pub_armed;                     // the last stage-5 launch publishes into slot pub_slot
-  int pub_slot;
-  // gated steps (f4, pft_slab_gate_*): the host's decisions on the next step go to a ring of
-  // pinned slots (4 words: seq, t bits, h bits, pad); the speculative stage 1's extra workgroup
-  // copies its slot into the device ring, which the pre-enqueued launches of that step read
-  unsigned long long* gate_pin;      // host address, PFT_GATE_SLOTS x 4 words
-  unsigned long long* gate_pin_dev;  // its device address
-  unsigned long long* gate_dev;      // device ring, PFT_GATE_SLOTS x 4 words
-  unsigned long long gate_seq;       // the last sequence number handed out
-  unsigned long long gate_arm_seq;   // the next speculative stage-1 launch decides this step ...
-  double gate_arm_t, gate_arm_h;     // ... (t, h) of it (ignored when that launch is gated itself)
-  unsigned long long gate_use_seq;   // launches enqueued now are gated on this decision (0: not)
-  double gate_final, gate_delta, gate_hmin;   // the solve's constants (pft_slab_gate_config)
-  int gate_local, gate_nan;
-  int gate_flip;         // test hook, env PFT_GATE_FLIP (StageArgs::d_flip)
-  // eps-publication bookkeeping snapshots (pft_slab_book_save/load): the launches of the next
-  // step are enqueued between this step's launches and the read of its error norm
-  struct Book {
-    long pub_next;
-    int pub_armed, pub_slot, eps_marked, defer_n, defer_slot;
-  } book[2];
-  int kz;                // planes per workgroup z-march; 0 = automatic (z-chunk cost model)
-  int n_cu;               // compute units of the slab's device
-  int cu_reserved;        // of them kept off the compute stream for the boundary launches (CU mask)
-  double* noise;         // device u_noise (n3*plane) or null
-  int tile_wx;           // 32 / 16: LDS-tiled kernels with that many pairs per row; 1: automatic;
-                         // 2: LDS-tiled at any size, automatic tile; 0: cache-based
-  int n1_tiled_ok;
-  int recompute;         // 1: stage inputs rebuilt from x and the K's (no aux arrays)
-  int gl_keep;           // X and XN hold the same gl, and x + c*0.0 == x for every gl value
-  int pair_on;           // pair kernels (merson_pair): 0 off, 1 automatic (large slabs), 2 wherever
-                         // they fit (pft_slab_set_pair); env PFT_PAIR overrides
-  int pair_env;          // PFT_PAIR was set
-  int pair_tx, pair_ty;  // pair tile (pair_geometry, once per slab); 0 x 0: none fits
-  long pair_ntile;
-  // f5 diagnostics (pft_slab_diag): device accumulators (PFT_DIAG_HEAD words, then one ice count
-  // per interior plane) and their pinned host copy, allocated by the first call
-  unsigned long long* diag_dev;
-  unsigned long long* diag_host;     // pinned
-  int diag_wgs;          // cap on the reduction's workgroups; 0: 8 per CU (env PFT_DIAG_WGS: A/B, tests)
-  int diag_timing;       // 1: HIP events around the kernel (pft_slab_diag_timing)
-  hipEvent_t ev_diag[2];
-  // f6 means (pft_slab_means): the slab's record, then one record per interior plane, and their
-  // pinned host copy, allocated by the first call; events around the kernel pair
-  unsigned long long* means_dev;
-  unsigned long long* means_host;    // pinned
-  int means_timing;
-  hipEvent_t ev_means[2];
-  // f7 snapshots (pft_slab_snapshot_export / pft_slab_image): the image-sized pinned, host-mapped
-  // buffer the background writer reads (allocated by the first call, freed at destroy once the
-  // writer is done with it), the device staging image of the staged host link, events around the
-  // export kernel
-  void* snap_host;
-  void* snap_host_dev;   // its device address
-  void* snap_stage;
-  int snap_timing;
-  hipEvent_t ev_snap[2];
-  double timeout_s;    // bound on a host wait for the compute stream while ipc peers are on
-                         // (env PFT_IPC_TIMEOUT, default 300 s; slab_wait)
-  pft_slab_watch_fn watch;   // communicator watchdog (RCCL: async error / expiry -> abort)
-  void* watch_ctx;
-  double watch_timeout_s;
-  // per-stage timing: a ring of begin/end event pairs, so that kernels still running when the
-  // host collects (the speculative stage 1) are picked up by a later collect
-  hipEvent_t tev[6][PFT_TRING][2];
-  int thead[6], ttail[6];      // next slot to record / oldest slot not yet collected
-  double tacc_ms[6];           // collected but not yet handed out
-  long tacc_n[6];
-};
-
 static double wall_s()
 {
   struct timespec t;
@@ -2452,7 +2256,7 @@ static double wall_s()
 // s->timeout_s the slab raises its own flag words past every sequence number (on the side stream,
 // which nothing blocks): the compute stream drains -- its results are void -- and the caller gets
 // PFT_ERR_IPC_TIMEOUT, which RK_MPI_SA_solve reports as PFT_SOLVE_DEVICE_ERROR.
-static int slab_poisoned(pft_slab* s, const char* what)
+int slab_poisoned(pft_slab* s, const char* what)
 {
   if (s->ipc_poisoned == 2) {
     snprintf(g_err, sizeof(g_err), "%s: the slab's communicator was aborted (PFT_COMM_TIMEOUT or an asynchronous error)", what);
@@ -2500,7 +2304,7 @@ static int slab_timed_out(pft_slab* s, const char* what)
 
 // the host waits for an event (or the whole compute stream when ev is null): unbounded with no ipc
 // peer, bounded by s->timeout_s with one
-static int slab_wait(pft_slab* s, hipEvent_t ev, const char* what)
+int slab_wait(pft_slab* s, hipEvent_t ev, const char* what)
 {
   if (s->ipc_poisoned) {
     // ipc: the released flags let the stream drain: wait for it, then refuse.  An aborted
@@ -2846,928 +2650,12 @@ int pft_slab_download_host(pft_slab* s, int which, double* host_padded)
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------
-// f5: the ice diagnostics of a state (pft_diag.h) -- a streaming reduction over the interior of
-// the three fields, each one contiguous run of n = n3 * plane doubles from plane 1 (no x/y ghosts).
-//
-// Everything is an integer: counts are added as 64-bit integers, maxima and minima go through
-// diag_key, a 64-bit key that orders every non-NaN double as the double orders (and -0.0 below
-// +0.0), so the same bits come out for any grid, chunking or arrival order.  Key 0 belongs to no
-// non-NaN double: a zeroed accumulator means "no value yet", and the minimum is kept as the maximum
-// of the complemented key, so one hipMemsetAsync per call resets every word.
-//
-// Work: the run is cut into 16-byte pairs (pair q = elements 2q - head, 2q - head + 1; head = 1
-// if the run started on an odd multiple of 8 bytes -- with the slab's layout it does not -- and the
-// first and the last pair may hold one element).  Workgroup b takes per_wg consecutive pairs and
-// indexes its elements from its first pair's (32-bit r); per iteration each wave takes 512
-// consecutive elements, four 16-byte loads per lane and field, all issued before the first use, so
-// a wave meets the planes in ascending order.  Where the 512 lie inside the run (all but the first
-// and last iteration of the grid) no element is tested for validity; elsewhere each is loaded alone
-// under its own test.  Counts come from __ballot and popcount and stay in scalar registers; the ice
-// count of the iteration goes to its plane -- one add when the 512 elements lie in one plane, else
-// one ballot round per plane touched -- into an LDS window of the workgroup's first PFT_DIAG_WIN
-// planes (past the window: the plane's global word).  At the end the keys are reduced across the
-// lanes and, through LDS, across the four waves: one set of global atomics per workgroup, plus
-// one per plane it touched.  (A first version with one pair per lane and iteration and 64-bit
-// bookkeeping ran at 3.5 TB/s, bound by scalar instruction issue: DESIGN.md section 7, f5.)
-#define PFT_DBLOCK 256
-#define PFT_DIAG_UNROLL 4                               // 16-byte loads per lane, field and iteration
-#define PFT_DIAG_WAVE_ELEMS (128 * PFT_DIAG_UNROLL)    // elements of a wave's iteration
-#define PFT_DIAG_WG_PAIRS (PFT_DBLOCK * PFT_DIAG_UNROLL)
-#define PFT_DIAG_HEAD 16   // accumulator words before the per-plane counts
-#define PFT_DIAG_WIN 64
-enum { DG_ICE = 0, DG_PORE, DG_ICE_PORE, DG_NONFINITE, DG_ICE_U, DG_U_MAX, DG_U_MIN, DG_P_MAX, DG_P_MIN, DG_WORDS };
-
-__host__ __device__ static inline unsigned long long diag_key(double x)
-{
-  unsigned long long b;
-  memcpy(&b, &x, 8);
-  return (b >> 63) ? ~b : (b | (1ULL << 63));
-}
-static double diag_unkey(unsigned long long k)
-{
-  const unsigned long long b = (k >> 63) ? (k & ~(1ULL << 63)) : ~k;
-  double x;
-  memcpy(&x, &b, 8);
-  return x;
-}
-
-__device__ __forceinline__ bool diag_finite(double x) { return fabs(x) < __builtin_inf(); }   // false on NaN
-
-struct DiagState {
-  unsigned long long c_ice, c_pore, c_both, c_nf;     // wave-uniform counts
-  unsigned long long iu, umax, umin, pmax, pmin;      // per-lane keys
-  int k, lo, hi;   // the wave's running plane: index from the workgroup's first, elements [lo, hi) (r)
-};
-
-// one iteration of a wave: elements r0 .. r0 + 511 of the workgroup (of them [r_lo, r_hi) exist;
-// FULL: all do).  fu/fp/fg point at the workgroup's element 0.
-template <bool FULL>
-__device__ __forceinline__ void diag_iter(DiagState& st, const double* __restrict__ fu, const double* __restrict__ fp,
-                                          const double* __restrict__ fg, int r0, int r_lo, int r_hi, int plane,
-                                          int lane, double p_thr, double gl_thr, unsigned long long* s_win,
-                                          unsigned long long* __restrict__ acc_planes)
-{
-  constexpr int NE = 2 * PFT_DIAG_UNROLL;
-  double u[NE], p[NE], g[NE];
-  bool v[NE], ice[NE];
-#pragma unroll
-  for (int j = 0; j < PFT_DIAG_UNROLL; ++j) {
-    const int r = r0 + 128 * j + 2 * lane;
-    if (FULL) {
-      const double2 a = *reinterpret_cast<const double2*>(fu + r);
-      const double2 b = *reinterpret_cast<const double2*>(fp + r);
-      const double2 c = *reinterpret_cast<const double2*>(fg + r);
-      u[2 * j] = a.x, u[2 * j + 1] = a.y, p[2 * j] = b.x, p[2 * j + 1] = b.y, g[2 * j] = c.x, g[2 * j + 1] = c.y;
-      v[2 * j] = v[2 * j + 1] = true;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const bool ok = r + i >= r_lo && r + i < r_hi;
-        v[2 * j + i] = ok;
-        u[2 * j + i] = ok ? fu[r + i] : 0.0;
-        p[2 * j + i] = ok ? fp[r + i] : 0.0;
-        g[2 * j + i] = ok ? fg[r + i] : 0.0;
-      }
-    }
-  }
-  unsigned it_ice = 0;
-#pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    // ordered comparisons: false on NaN
-    ice[i] = v[i] && p[i] > p_thr;
-    const bool por = v[i] && g[i] < gl_thr;
-    const bool nf = v[i] && !(diag_finite(u[i]) && diag_finite(p[i]) && diag_finite(g[i]));
-    it_ice += (unsigned)__popcll(__ballot(ice[i]));
-    st.c_pore += __popcll(__ballot(por));
-    st.c_both += __popcll(__ballot(ice[i] && por));
-    st.c_nf += __popcll(__ballot(nf));
-    if (v[i] && u[i] == u[i]) {
-      const unsigned long long k = diag_key(u[i]);
-      st.umax = k > st.umax ? k : st.umax;
-      st.umin = ~k > st.umin ? ~k : st.umin;
-      if (ice[i]) {
-        const unsigned long long a = (unsigned long long)__double_as_longlong(fabs(u[i]));
-        st.iu = a > st.iu ? a : st.iu;   // non-negative doubles order as their bits
-      }
-    }
-    if (v[i] && p[i] == p[i]) {
-      const unsigned long long k = diag_key(p[i]);
-      st.pmax = k > st.pmax ? k : st.pmax;
-      st.pmin = ~k > st.pmin ? ~k : st.pmin;
-    }
-  }
-  st.c_ice += it_ice;
-  // the ice counts of the planes the wave's existing elements [w0, w1] lie in
-  const int w0 = FULL ? r0 : (r0 > r_lo ? r0 : r_lo);
-  const int w1 = (FULL ? r0 + PFT_DIAG_WAVE_ELEMS : (r0 + PFT_DIAG_WAVE_ELEMS < r_hi ? r0 + PFT_DIAG_WAVE_ELEMS : r_hi)) - 1;
-  if (w1 < w0) return;
-  while (w0 >= st.hi) {
-    ++st.k;
-    st.lo = st.hi;
-    st.hi += plane;
-  }
-  const bool one_plane = w1 < st.hi;
-  while (true) {
-    unsigned c = it_ice;
-    if (!one_plane) {
-      c = 0;
-#pragma unroll
-      for (int i = 0; i < NE; ++i) {
-        const int r = r0 + 128 * (i >> 1) + 2 * lane + (i & 1);
-        c += (unsigned)__popcll(__ballot(ice[i] && r >= st.lo && r < st.hi));
-      }
-    }
-    if (lane == 0 && c) {
-      if (st.k < PFT_DIAG_WIN)
-        atomicAdd(&s_win[st.k], (unsigned long long)c);
-      else
-        atomicAdd(&acc_planes[st.k], (unsigned long long)c);
-    }
-    if (w1 < st.hi) break;
-    ++st.k;
-    st.lo = st.hi;
-    st.hi += plane;
-  }
-}
-
-__global__ __launch_bounds__(PFT_DBLOCK) void diag_kernel(const double* __restrict__ fu, const double* __restrict__ fp,
-                                                          const double* __restrict__ fg, long n, int plane, int head,
-                                                          long nq, long per_wg, double p_thr, double gl_thr,
-                                                          unsigned long long* __restrict__ acc)
-{
-  __shared__ unsigned long long s_win[PFT_DIAG_WIN];
-  __shared__ unsigned long long s_red[PFT_DBLOCK / 64][DG_WORDS];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long q_begin = (long)blockIdx.x * per_wg;
-  const long q_end = q_begin + per_wg < nq ? q_begin + per_wg : nq;
-  for (int i = threadIdx.x; i < PFT_DIAG_WIN; i += PFT_DBLOCK) s_win[i] = 0;
-  __syncthreads();
-  // the workgroup's elements r = 0 .. span - 1 stand for e_base + r of the run; of them [r_lo, r_hi)
-  // exist (e_base = -1: the slot before the run; the last pair's second slot may lie past its end)
-  const long e_base = 2 * q_begin - head;
-  const int span = (int)(2 * (q_end - q_begin));
-  const int r_lo = e_base < 0 ? 1 : 0;
-  const int r_hi = n - e_base < span ? (int)(n - e_base) : span;
-  const long k_base = (e_base > 0 ? e_base : 0) / plane;   // the first plane this workgroup touches
-  DiagState st;
-  st.c_ice = st.c_pore = st.c_both = st.c_nf = 0;
-  st.iu = st.umax = st.umin = st.pmax = st.pmin = 0;
-  st.k = 0;
-  st.lo = (int)(k_base * plane - e_base);
-  st.hi = st.lo + plane;
-  const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
-  const double* wp = fp + e_base;
-  const double* wg = fg + e_base;
-  unsigned long long* acc_planes = acc + PFT_DIAG_HEAD + k_base;
-
-  for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
-    if (r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi)
-      diag_iter<true>(st, wu, wp, wg, r0, r_lo, r_hi, plane, lane, p_thr, gl_thr, s_win, acc_planes);
-    else
-      diag_iter<false>(st, wu, wp, wg, r0, r_lo, r_hi, plane, lane, p_thr, gl_thr, s_win, acc_planes);
-  }
-
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    unsigned long long o;
-    o = __shfl_xor(st.iu, off, 64), st.iu = o > st.iu ? o : st.iu;
-    o = __shfl_xor(st.umax, off, 64), st.umax = o > st.umax ? o : st.umax;
-    o = __shfl_xor(st.umin, off, 64), st.umin = o > st.umin ? o : st.umin;
-    o = __shfl_xor(st.pmax, off, 64), st.pmax = o > st.pmax ? o : st.pmax;
-    o = __shfl_xor(st.pmin, off, 64), st.pmin = o > st.pmin ? o : st.pmin;
-  }
-  if (lane == 0) {
-    unsigned long long* r = s_red[wave];
-    r[DG_ICE] = st.c_ice, r[DG_PORE] = st.c_pore, r[DG_ICE_PORE] = st.c_both, r[DG_NONFINITE] = st.c_nf;
-    r[DG_ICE_U] = st.iu, r[DG_U_MAX] = st.umax, r[DG_U_MIN] = st.umin, r[DG_P_MAX] = st.pmax, r[DG_P_MIN] = st.pmin;
-  }
-  __syncthreads();
-  if (threadIdx.x < DG_WORDS) {
-    // one thread per accumulator word: the waves' partials, then one atomic
-    const int w = threadIdx.x;
-    unsigned long long x = s_red[0][w];
-    for (int i = 1; i < PFT_DBLOCK / 64; ++i) {
-      const unsigned long long o = s_red[i][w];
-      x = w <= DG_NONFINITE ? x + o : (o > x ? o : x);
-    }
-    if (x) {
-      if (w <= DG_NONFINITE)
-        atomicAdd(&acc[w], x);
-      else
-        atomicMax(&acc[w], x);
-    }
-  }
-  if (threadIdx.x >= 64 && threadIdx.x < 64 + PFT_DIAG_WIN) {
-    const int t = threadIdx.x - 64;
-    const unsigned long long x = s_win[t];
-    if (x) atomicAdd(&acc_planes[t], x);
-  }
-}
-
-extern "C" {
-
-int pft_slab_diag(pft_slab* s, int buf, const pft_diag_opts* opts, pft_diag* out, long long* ice_per_plane)
-{
-  if (!s || !out || buf < 0 || buf >= PFT_BUF_COUNT) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_diag");
-  const long plane = s->plane, n = (long)s->d.n3 * plane;
-  const size_t bytes = sizeof(unsigned long long) * (size_t)(PFT_DIAG_HEAD + s->d.n3);
-  if (!s->diag_dev) HIPCHK(hipMalloc((void**)&s->diag_dev, bytes));
-  if (!s->diag_host) HIPCHK(hipHostMalloc((void**)&s->diag_host, bytes, hipHostMallocDefault));
-  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
-  const double* fu = s->buf[buf] + plane;
-  const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
-  const long nq = (n + head + 1) / 2;
-  if (plane > (1L << 30)) return -2;   // (the kernel's 32-bit plane bounds)
-  // at most `cap` workgroups (all resident at once: 8 per CU), each a whole number of iterations
-  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
-  long wgs = (nq + PFT_DIAG_WG_PAIRS - 1) / PFT_DIAG_WG_PAIRS;
-  if (wgs > cap) wgs = cap;
-  const long wgs_min = (nq >> 29) + 1;   // a workgroup indexes its elements with 32 bits
-  if (wgs < wgs_min) wgs = wgs_min;
-  const long per_wg = ((nq + wgs - 1) / wgs + PFT_DIAG_WG_PAIRS - 1) / PFT_DIAG_WG_PAIRS * PFT_DIAG_WG_PAIRS;
-  wgs = (nq + per_wg - 1) / per_wg;
-  const double p_thr = opts ? opts->p_thr : 0.5, gl_thr = opts ? opts->gl_thr : 0.5;
-  // no state carries over between calls: every accumulator word is zeroed on the stream first
-  HIPCHK(hipMemsetAsync(s->diag_dev, 0, bytes, s->stream));
-  if (s->diag_timing) HIPCHK(hipEventRecord(s->ev_diag[0], s->stream));
-  diag_kernel<<<(unsigned)wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, n, (int)plane, head, nq, per_wg,
-                                                           p_thr, gl_thr, s->diag_dev);
-  HIPCHK(hipGetLastError());
-  if (s->diag_timing) HIPCHK(hipEventRecord(s->ev_diag[1], s->stream));
-  HIPCHK(hipMemcpyAsync(s->diag_host, s->diag_dev, bytes, hipMemcpyDeviceToHost, s->stream));
-  // the slab's bounded wait: an ipc peer's timeout or an aborted communicator ends it, as for the
-  // error norm
-  const int rc = slab_wait(s, nullptr, "pft_slab_diag");
-  if (rc) return rc;
-  const unsigned long long* h = s->diag_host;
-  out->cells = n;
-  out->ice = (long long)h[DG_ICE];
-  out->pore = (long long)h[DG_PORE];
-  out->ice_pore = (long long)h[DG_ICE_PORE];
-  out->nonfinite = (long long)h[DG_NONFINITE];
-  memcpy(&out->ice_u_maxabs, &h[DG_ICE_U], 8);
-  const double inf = __builtin_inf();
-  out->u_max = h[DG_U_MAX] ? diag_unkey(h[DG_U_MAX]) : -inf;
-  out->u_min = h[DG_U_MIN] ? diag_unkey(~h[DG_U_MIN]) : inf;
-  out->p_max = h[DG_P_MAX] ? diag_unkey(h[DG_P_MAX]) : -inf;
-  out->p_min = h[DG_P_MIN] ? diag_unkey(~h[DG_P_MIN]) : inf;
-  if (ice_per_plane)
-    for (int k = 0; k < s->d.n3; ++k) ice_per_plane[k] = (long long)h[PFT_DIAG_HEAD + k];
-  return 0;
-}
-
-int pft_slab_diag_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_diag[i]) HIPCHK(hipEventCreate(&s->ev_diag[i]));
-  s->diag_timing = on ? 1 : 0;
-  return 0;
-}
-
-int pft_slab_diag_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->diag_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_diag[0], s->ev_diag[1]));
-  *ms = f;
-  return 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// f7: the snapshot image of a state (pft_io.h) -- for q = u, p, gl in turn the slab's n3*n1*n2
-// interior doubles as big-endian 8-byte words, the bytes the slab owns in each variable of the
-// dataset.  In the slab's layout a field's interior is one contiguous run from plane 1, i fastest
-// (what diag_kernel streams), which is the [n3][n2][n1] order of the dataset's variable, so the
-// export is a byte swap of three runs and the import its inverse.  One flat streaming kernel for
-// both directions, blockIdx.y the field: the run is taken in 16-byte pairs from the first 16-byte
-// boundary of the slab's side, PFT_SNAP_NV pairs per lane and iteration, all loaded before the
-// first is used; the pair's words are swapped as integers (a pure bit move: NaN payloads, -0.0 and
-// subnormals survive) and stored as one 16-byte store, or as two 8-byte stores when the image's
-// side of that field is only 8-byte aligned (an odd run length puts the second field there).  The
-// element before the first pair (an odd `head`) and the one after the last (an odd rest) are moved
-// by one lane.  No LDS; the export has no atomic at all.  Ghost and far ghost planes are never
-// touched.  The import writes X and XN, as the device IC does, and reports whether a gl value is
-// -0.0 or NaN (pft_slab_set_gl_keep): a ballot per wave and one integer atomic.
-
-#define PFT_SNAP_BLOCK 256
-#define PFT_SNAP_NV 4
-#define PFT_SNAP_WG_PAIRS (PFT_SNAP_BLOCK * PFT_SNAP_NV)
-
-typedef unsigned long long snap_u64;
-
-__device__ __forceinline__ bool snap_gl_unclean(snap_u64 v)
-{
-  // -0.0, or NaN (exponent all ones, mantissa non-zero)
-  return v == 0x8000000000000000ULL || (v & 0x7fffffffffffffffULL) > 0x7ff0000000000000ULL;
-}
-
-// one iteration of a workgroup: PFT_SNAP_NV pairs per lane from pair p0 on.  FULL: all of them lie
-// in the run, and the code is straight-line -- every load is issued before the first swap; else a
-// pair past the run's end loads the last pair instead and is not stored.  S16 / D16: that side
-// takes 16-byte accesses
-template <bool IMPORT, bool S16, bool D16, bool FULL>
-__device__ __forceinline__ bool snap_iter(const snap_u64* __restrict__ sp, snap_u64* __restrict__ dp,
-                                          snap_u64* __restrict__ dp2, long p0, long m, bool scan)
-{
-  bool bad = false;
-  snap_u64 a[PFT_SNAP_NV], b[PFT_SNAP_NV];
-#pragma unroll
-  for (int i = 0; i < PFT_SNAP_NV; ++i) {
-    const long p = p0 + (long)i * PFT_SNAP_BLOCK, pc = (FULL || p < m) ? p : m - 1;
-    if (S16) {
-      const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(sp + 2 * pc);
-      a[i] = v.x;
-      b[i] = v.y;
-    } else {
-      a[i] = sp[2 * pc];
-      b[i] = sp[2 * pc + 1];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < PFT_SNAP_NV; ++i) {
-    const long p = p0 + (long)i * PFT_SNAP_BLOCK;
-    if (FULL || p < m) {
-      const snap_u64 x = __builtin_bswap64(a[i]), y = __builtin_bswap64(b[i]);
-      if (IMPORT && scan) bad = bad || snap_gl_unclean(x) || snap_gl_unclean(y);
-      if (D16) {
-        ulonglong2 v;
-        v.x = x;
-        v.y = y;
-        *reinterpret_cast<ulonglong2*>(dp + 2 * p) = v;
-        if (IMPORT) *reinterpret_cast<ulonglong2*>(dp2 + 2 * p) = v;
-      } else {
-        dp[2 * p] = x;
-        dp[2 * p + 1] = y;
-        if (IMPORT) {
-          dp2[2 * p] = x;
-          dp2[2 * p + 1] = y;
-        }
-      }
-    }
-  }
-  return bad;
-}
-
-// pairs [0, m) of sp -> dp (and dp2)
-template <bool IMPORT, bool S16, bool D16>
-__device__ __forceinline__ bool snap_run(const snap_u64* __restrict__ sp, snap_u64* __restrict__ dp,
-                                         snap_u64* __restrict__ dp2, long m, bool scan)
-{
-  bool bad = false;
-  for (long c = blockIdx.x; c * PFT_SNAP_WG_PAIRS < m; c += gridDim.x) {
-    const long p0 = c * PFT_SNAP_WG_PAIRS + threadIdx.x;
-    if ((c + 1) * PFT_SNAP_WG_PAIRS <= m)
-      bad = snap_iter<IMPORT, S16, D16, true>(sp, dp, dp2, p0, m, scan) || bad;
-    else
-      bad = snap_iter<IMPORT, S16, D16, false>(sp, dp, dp2, p0, m, scan) || bad;
-  }
-  return bad;
-}
-
-// src / dst: word 0 of field 0's run on either side, strides in words; n words per field.  IMPORT:
-// dst2 is the second state buffer (the same alignment as dst: checked by the host)
-template <bool IMPORT>
-__global__ __launch_bounds__(PFT_SNAP_BLOCK) void snap_kernel(const snap_u64* __restrict__ src, long src_stride,
-                                                              snap_u64* __restrict__ dst, snap_u64* __restrict__ dst2,
-                                                              long dst_stride, long n, unsigned int* __restrict__ unclean)
-{
-  const int q = blockIdx.y;
-  const snap_u64* sp = src + (long)q * src_stride;
-  snap_u64* dp = dst + (long)q * dst_stride;
-  snap_u64* dp2 = IMPORT ? dst2 + (long)q * dst_stride : nullptr;
-  const bool scan = IMPORT && q == 2;
-  // the slab's side decides where the pairs begin; the image's side follows
-  const uintptr_t slab_side = IMPORT ? (uintptr_t)dp : (uintptr_t)sp;
-  const long head = (n > 0 && ((slab_side >> 3) & 1)) ? 1 : 0;
-  const long m = (n - head) / 2;
-  const bool tail = ((n - head) & 1) != 0;
-  const uintptr_t image_side = IMPORT ? (uintptr_t)(sp + head) : (uintptr_t)(dp + head);
-  bool bad;
-  if ((image_side & 15) == 0)
-    bad = snap_run<IMPORT, true, true>(sp + head, dp + head, IMPORT ? dp2 + head : nullptr, m, scan);
-  else if (IMPORT)
-    bad = snap_run<IMPORT, false, true>(sp + head, dp + head, dp2 + head, m, scan);
-  else
-    bad = snap_run<IMPORT, true, false>(sp + head, dp + head, nullptr, m, scan);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // the run's ends, element-wise
-    if (head) {
-      const snap_u64 x = __builtin_bswap64(sp[0]);
-      if (scan) bad = bad || snap_gl_unclean(x);
-      dp[0] = x;
-      if (IMPORT) dp2[0] = x;
-    }
-    if (tail) {
-      const snap_u64 x = __builtin_bswap64(sp[n - 1]);
-      if (scan) bad = bad || snap_gl_unclean(x);
-      dp[n - 1] = x;
-      if (IMPORT) dp2[n - 1] = x;
-    }
-  }
-  if (IMPORT) {
-    const unsigned long long any = __ballot(bad);
-    if (scan && any && (threadIdx.x & 63) == 0) atomicOr(unclean, 1u);
-  }
-}
-
-static unsigned snap_blocks(const pft_slab* s, long n)
-{
-  // all resident at once (8 workgroups per CU), each a whole number of iterations
-  const long cap = 8L * (s->n_cu > 0 ? s->n_cu : 256);
-  long wgs = (n / 2 + PFT_SNAP_WG_PAIRS - 1) / PFT_SNAP_WG_PAIRS;
-  if (wgs < 1) wgs = 1;
-  return (unsigned)(wgs > cap ? cap : wgs);
-}
-
-// the export kernel of buffer `buf` into dst, enqueued on the compute stream (no wait)
-static int snap_export_enqueue(pft_slab* s, int buf, void* dst)
-{
-  const long n = (long)s->d.n3 * s->plane;
-  const snap_u64* src = reinterpret_cast<const snap_u64*>(s->buf[buf] + s->plane);   // plane 1: the interior
-  if (s->snap_timing) HIPCHK(hipEventRecord(s->ev_snap[0], s->stream));
-  snap_kernel<false><<<dim3(snap_blocks(s, n), 3), PFT_SNAP_BLOCK, 0, s->stream>>>(src, s->fs, (snap_u64*)dst, nullptr, n, n,
-                                                                                   nullptr);
-  HIPCHK(hipGetLastError());
-  if (s->snap_timing) HIPCHK(hipEventRecord(s->ev_snap[1], s->stream));
-  return 0;
-}
-
-static int snap_ensure_host(pft_slab* s)
-{
-  if (s->snap_host) return 0;
-  const size_t bytes = 3 * sizeof(double) * (size_t)s->d.n3 * (size_t)s->plane;
-  HIPCHK(hipHostMalloc(&s->snap_host, bytes, hipHostMallocMapped));
-  const hipError_t e = hipHostGetDevicePointer(&s->snap_host_dev, s->snap_host, 0);
-  if (e != hipSuccess) {
-    (void)hipHostFree(s->snap_host);
-    s->snap_host = s->snap_host_dev = nullptr;
-    return fail(e, "hipHostGetDevicePointer (snapshot image)");
-  }
-  return 0;
-}
-
-extern "C" {
-
-size_t pft_slab_image_bytes(const pft_slab* s)
-{
-  return s ? 3 * sizeof(double) * (size_t)s->d.n3 * (size_t)s->plane : 0;
-}
-
-int pft_slab_export_be(pft_slab* s, int buf, void* dst)
-{
-  if (!s || !dst || buf < 0 || buf >= PFT_BUF_COUNT || ((uintptr_t)dst & 7)) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_export_be");
-  const int rc = snap_export_enqueue(s, buf, dst);
-  if (rc) return rc;
-  return slab_wait(s, nullptr, "pft_slab_export_be");
-}
-
-int pft_slab_import_be(pft_slab* s, const void* src, int* gl_unclean)
-{
-  if (!s || !src || ((uintptr_t)src & 7)) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_import_be");
-  const long n = (long)s->d.n3 * s->plane;
-  snap_u64* x = reinterpret_cast<snap_u64*>(s->buf[PFT_BUF_X] + s->plane);
-  snap_u64* xn = reinterpret_cast<snap_u64*>(s->buf[PFT_BUF_XN] + s->plane);
-  if ((((uintptr_t)x ^ (uintptr_t)xn) & 15) != 0) return -2;   // (every buffer is allocated alike)
-  // X and XN change: the caller re-establishes gl_keep from *gl_unclean, as after a device IC
-  s->gl_keep = 0;
-  unsigned int* flag = reinterpret_cast<unsigned int*>(s->scratch + 4);   // (words 0, 1: the error norm's)
-  HIPCHK(hipMemsetAsync(flag, 0, sizeof(unsigned int), s->stream));
-  snap_kernel<true><<<dim3(snap_blocks(s, n), 3), PFT_SNAP_BLOCK, 0, s->stream>>>((const snap_u64*)src, n, x, xn, s->fs, n, flag);
-  HIPCHK(hipGetLastError());
-  unsigned int* hflag = reinterpret_cast<unsigned int*>(s->host_scratch + 4);
-  HIPCHK(hipMemcpyAsync(hflag, flag, sizeof(unsigned int), hipMemcpyDeviceToHost, s->stream));
-  const int rc = slab_wait(s, nullptr, "pft_slab_import_be");
-  if (rc) return rc;
-  if (gl_unclean) *gl_unclean = *hflag ? 1 : 0;
-  return 0;
-}
-
-int pft_slab_image(pft_slab* s, void** host, void** dev)
-{
-  if (!s) return -2;
-  const int rc = snap_ensure_host(s);
-  if (rc) return rc;
-  if (host) *host = s->snap_host;
-  if (dev) *dev = s->snap_host_dev;
-  return 0;
-}
-
-int pft_slab_snapshot_export(pft_slab* s, int buf, int link, void** image)
-{
-  if (!s || !image || buf < 0 || buf >= PFT_BUF_COUNT || link < 0 || link > 1) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_snapshot_export");
-  int rc = snap_ensure_host(s);
-  if (rc) return rc;
-  // a job of the background writer may still read the buffer's previous image
-  (void)pft_snapshot_writer_release(s->snap_host);
-  if (link == PFT_SNAP_LINK_DIRECT) {
-    if ((rc = snap_export_enqueue(s, buf, s->snap_host_dev))) return rc;
-  } else {
-    const size_t bytes = pft_slab_image_bytes(s);
-    if (!s->snap_stage) HIPCHK(hipMalloc(&s->snap_stage, bytes));
-    if ((rc = snap_export_enqueue(s, buf, s->snap_stage))) return rc;
-    HIPCHK(hipMemcpyAsync(s->snap_host, s->snap_stage, bytes, hipMemcpyDeviceToHost, s->stream));
-  }
-  if ((rc = slab_wait(s, nullptr, "pft_slab_snapshot_export"))) return rc;
-  *image = s->snap_host;
-  return 0;
-}
-
-int pft_slab_snapshot_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_snap[i]) HIPCHK(hipEventCreate(&s->ev_snap[i]));
-  s->snap_timing = on ? 1 : 0;
-  return 0;
-}
-
-int pft_slab_snapshot_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->snap_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_snap[0], s->ev_snap[1]));
-  *ms = f;
-  return 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// f6: the exact sums of a state (pft_means.h) -- the same streaming read as diag_kernel, but every
-// double is split into its three 32-bit digits (pft_means.h: word index c, digits of M << s) and
-// the digits are added as 64-bit integers, so the words that come out are those of pft_means_host
-// for any grid, chunking or arrival order.  No floating-point add, no compare-and-swap.
-//
-// Work: an item is a contiguous segment (seg_len elements, a multiple of a workgroup's iteration)
-// of one interior plane; a workgroup takes items blockIdx.x, + gridDim.x, ... and for each one
-// accumulates into an LDS copy of a pft_means record (268 words, 2 144 bytes), then adds its
-// non-zero words to that plane's record in global memory: one integer atomic per word, the
-// workgroups of different planes on different words.  means_total_kernel adds the planes' records.
-// An item is read as diag_kernel reads its share: 16-byte pairs, per iteration each wave 512
-// consecutive elements, four 16-byte loads per lane and field all issued before the first use;
-// where the 512 do not all lie inside the item (its first and last iteration at most) each element
-// is loaded alone under its own test.
-//
-// Contention is taken out on chip.  u -- and p away from the interface's tails -- lies in one
-// 32-exponent window for every lane (word 32 for anything in [4, 2^34)), so a wave keeps a
-// wave-uniform current word index `cur` per summand (MeansPair: the sum over all cells and the
-// masked sum share the summand's digits) and each lane adds its digits to three 64-bit registers
-// per sum.  Inactive lanes (zeros, NaN, +-Inf, slots outside the item) have zero digits and do not
-// disturb that.  One ballot per iteration and summand tells whether some active lane has another
-// index; only then the eight slots are taken one by one: a slot none of whose active lanes is at
-// `cur` flushes the registers (a shuffle reduction, then lane 0 adds to LDS) and moves `cur` to
-// its first active lane's index; lanes at `cur` add in registers, the others add their digits to
-// LDS with per-lane 64-bit atomics.  Both ways add the same integers to the same words.  A second
-// ballot asks whether any active value is negative: without one (u in kelvin, p in [0, 1]) the
-// 32-bit digits are added as they are, with no negation and 32-bit selects for the masked sum.
-// A lane adds at most plane / 256 + 8 <= 2^22 + 8 digits below 2^32 between two flushes (an item
-// is at most a plane, PFT_MEANS_MAX_PLANE, and ends with a flush), so the wave's sum of 64 lanes
-// stays below 2^61; an LDS word takes a workgroup's share of one plane and a global word at most
-// 2^31 - 1 cells' digits: below 2^63.
-#define PFT_MEANS_REC (PFT_MEAN_COUNT * (PFT_XSUM_WORDS + 1))   // 64-bit words of a pft_means: n[4], sum[4][66]
-#define PFT_MEANS_MAX_PLANE (1L << 30)
-static_assert(sizeof(pft_means) == 8 * PFT_MEANS_REC, "pft_means is n[4] then sum[4][66], no padding");
-
-struct MeansPair {
-  long long a0, a1, a2;   // per lane: the digits added for the sum over all cells, words cur .. cur + 2
-  long long m0, m1, m2;   // the same for the masked sum
-  int cur;                // wave-uniform, 0 .. 63; kept across flushes (the first guess: the word of
-                          // u near 273 and of p near 1, wrong at the price of one slow iteration)
-};
-
-__device__ __forceinline__ long long means_wave_sum(long long v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// the wave's registers into the workgroup's LDS record: s_all / s_msk point at the two sums' words
-__device__ __forceinline__ void means_flush(MeansPair& st, int lane, unsigned long long* s_all, unsigned long long* s_msk)
-{
-  const long long a0 = means_wave_sum(st.a0), a1 = means_wave_sum(st.a1), a2 = means_wave_sum(st.a2);
-  const long long m0 = means_wave_sum(st.m0), m1 = means_wave_sum(st.m1), m2 = means_wave_sum(st.m2);
-  if (lane == 0) {
-    if (a0) atomicAdd(&s_all[st.cur], (unsigned long long)a0);
-    if (a1) atomicAdd(&s_all[st.cur + 1], (unsigned long long)a1);
-    if (a2) atomicAdd(&s_all[st.cur + 2], (unsigned long long)a2);
-    if (m0) atomicAdd(&s_msk[st.cur], (unsigned long long)m0);
-    if (m1) atomicAdd(&s_msk[st.cur + 1], (unsigned long long)m1);
-    if (m2) atomicAdd(&s_msk[st.cur + 2], (unsigned long long)m2);
-  }
-  st.a0 = st.a1 = st.a2 = st.m0 = st.m1 = st.m2 = 0;
-}
-
-// the three 32-bit digits of |x| (zero unless act) and its sign
-__device__ __forceinline__ void means_digits(double x, bool act, unsigned& e0, unsigned& e1, unsigned& e2, bool& neg)
-{
-  const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
-  const int E = (int)(bits >> 52) & 0x7ff;
-  const unsigned long long M = (bits & 0xfffffffffffffULL) | (E ? 1ULL << 52 : 0ULL);
-  const int s = ((E > 1 ? E : 1) - 1) & 31;
-  const unsigned long long lo = act ? M << s : 0ULL;                    // T = M << s = hi * 2^64 + lo
-  const unsigned long long hi = act ? (M >> 32) >> (32 - s) : 0ULL;     // (32 - s is 1..32; below 2^20)
-  e0 = (unsigned)lo, e1 = (unsigned)(lo >> 32), e2 = (unsigned)hi;
-  neg = (bits >> 63) != 0;
-}
-
-// the same as signed 64-bit integers
-__device__ __forceinline__ void means_signed_digits(double x, bool act, long long& d0, long long& d1, long long& d2)
-{
-  unsigned e0, e1, e2;
-  bool neg;
-  means_digits(x, act, e0, e1, e2, neg);
-  d0 = neg ? -(long long)e0 : (long long)e0, d1 = neg ? -(long long)e1 : (long long)e1;
-  d2 = neg ? -(long long)e2 : (long long)e2;
-}
-
-// the eight values x[] of a wave's iteration (v: the slot exists, msk: it enters the masked sum)
-// into st; n_all / n_msk: the wave-uniform counts of the cells that entered
-template <int NE, int I0, int I1>
-__device__ __forceinline__ void means_accumulate(MeansPair& st, const double (&x)[NE], const bool (&v)[NE],
-                                                 const bool (&msk)[NE], unsigned long long& n_all,
-                                                 unsigned long long& n_msk, int lane, unsigned long long* s_all,
-                                                 unsigned long long* s_msk)
-{
-  int c[NE];
-  bool act[NE];
-  bool other = false, minus = false;
-#pragma unroll
-  for (int i = I0; i < I1; ++i) {
-    const unsigned long long bits = (unsigned long long)__double_as_longlong(x[i]);
-    const int E = (int)(bits >> 52) & 0x7ff;
-    const bool fin = v[i] && E != 0x7ff;
-    act[i] = fin && (bits << 1) != 0;            // finite and not +-0
-    c[i] = ((E > 1 ? E : 1) - 1) >> 5;
-    n_all += __popcll(__ballot(fin));
-    n_msk += __popcll(__ballot(fin && msk[i]));
-    other |= act[i] && c[i] != st.cur;
-    minus |= act[i] && (bits >> 63) != 0;
-  }
-  const bool any_other = __ballot(other) != 0, any_minus = __ballot(minus) != 0;
-  if (!any_other && !any_minus) {
-    // every active lane of every slot is at cur and positive (u in kelvin, p in [0, 1]): the
-    // digits are added as they are, 32-bit values into the 64-bit registers
-#pragma unroll
-    for (int i = I0; i < I1; ++i) {
-      unsigned e0, e1, e2;
-      bool neg;
-      means_digits(x[i], act[i], e0, e1, e2, neg);
-      st.a0 += e0, st.a1 += e1, st.a2 += e2;
-      st.m0 += msk[i] ? e0 : 0u, st.m1 += msk[i] ? e1 : 0u, st.m2 += msk[i] ? e2 : 0u;
-    }
-    return;
-  }
-  if (!any_other) {
-    // every active lane of every slot is at cur, some are negative
-#pragma unroll
-    for (int i = I0; i < I1; ++i) {
-      long long d0, d1, d2;
-      means_signed_digits(x[i], act[i], d0, d1, d2);
-      st.a0 += d0, st.a1 += d1, st.a2 += d2;
-      st.m0 += msk[i] ? d0 : 0, st.m1 += msk[i] ? d1 : 0, st.m2 += msk[i] ? d2 : 0;
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = I0; i < I1; ++i) {
-    const unsigned long long m_act = __ballot(act[i]);
-    if (!m_act) continue;
-    if (!__ballot(act[i] && c[i] == st.cur)) {
-      means_flush(st, lane, s_all, s_msk);
-      st.cur = __builtin_amdgcn_readfirstlane(__shfl(c[i], (int)__ffsll((long long)m_act) - 1, 64));
-    }
-    long long d0, d1, d2;
-    means_signed_digits(x[i], act[i], d0, d1, d2);
-    const bool here = c[i] == st.cur;            // (inactive lanes: zero digits, either way nothing)
-    st.a0 += here ? d0 : 0, st.a1 += here ? d1 : 0, st.a2 += here ? d2 : 0;
-    st.m0 += here && msk[i] ? d0 : 0, st.m1 += here && msk[i] ? d1 : 0, st.m2 += here && msk[i] ? d2 : 0;
-    if (act[i] && !here) {
-      if (d0) atomicAdd(&s_all[c[i]], (unsigned long long)d0);
-      if (d1) atomicAdd(&s_all[c[i] + 1], (unsigned long long)d1);
-      if (d2) atomicAdd(&s_all[c[i] + 2], (unsigned long long)d2);
-      if (msk[i]) {
-        if (d0) atomicAdd(&s_msk[c[i]], (unsigned long long)d0);
-        if (d1) atomicAdd(&s_msk[c[i] + 1], (unsigned long long)d1);
-        if (d2) atomicAdd(&s_msk[c[i] + 2], (unsigned long long)d2);
-      }
-    }
-  }
-}
-
-struct MeansState {
-  MeansPair u, p;
-  unsigned long long n_u, n_p, n_ui, n_pp;   // wave-uniform counts
-};
-
-// one iteration of a wave: elements r0 .. r0 + 511 of the item's pair-aligned frame (of them
-// [r_lo, r_hi) belong to the item; FULL: all do).  fu/fp/fg point at the frame's element 0.
-template <bool FULL>
-__device__ __forceinline__ void means_iter(MeansState& st, const double* __restrict__ fu, const double* __restrict__ fp,
-                                           const double* __restrict__ fg, int r0, int r_lo, int r_hi, int lane,
-                                           double p_thr, double gl_thr, unsigned long long* s_rec)
-{
-  constexpr int NE = 2 * PFT_DIAG_UNROLL;
-  double u[NE], p[NE], g[NE];
-  bool v[NE], ice[NE], pore[NE];
-#pragma unroll
-  for (int j = 0; j < PFT_DIAG_UNROLL; ++j) {
-    const int r = r0 + 128 * j + 2 * lane;
-    if (FULL) {
-      const double2 a = *reinterpret_cast<const double2*>(fu + r);
-      const double2 b = *reinterpret_cast<const double2*>(fp + r);
-      const double2 c = *reinterpret_cast<const double2*>(fg + r);
-      u[2 * j] = a.x, u[2 * j + 1] = a.y, p[2 * j] = b.x, p[2 * j + 1] = b.y, g[2 * j] = c.x, g[2 * j + 1] = c.y;
-      v[2 * j] = v[2 * j + 1] = true;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const bool ok = r + i >= r_lo && r + i < r_hi;
-        v[2 * j + i] = ok;
-        u[2 * j + i] = ok ? fu[r + i] : 0.0;
-        p[2 * j + i] = ok ? fp[r + i] : 0.0;
-        g[2 * j + i] = ok ? fg[r + i] : 0.0;
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    // ordered comparisons: false on NaN
-    ice[i] = v[i] && p[i] > p_thr;
-    pore[i] = v[i] && g[i] < gl_thr;
-  }
-  unsigned long long* sums = s_rec + PFT_MEAN_COUNT;
-  // (in two halves: fewer lane masks alive at a time)
-  means_accumulate<NE, 0, NE / 2>(st.u, u, v, ice, st.n_u, st.n_ui, lane, sums + PFT_MEAN_U * PFT_XSUM_WORDS,
-                                  sums + PFT_MEAN_U_ICE * PFT_XSUM_WORDS);
-  means_accumulate<NE, 0, NE / 2>(st.p, p, v, pore, st.n_p, st.n_pp, lane, sums + PFT_MEAN_P * PFT_XSUM_WORDS,
-                                  sums + PFT_MEAN_P_PORE * PFT_XSUM_WORDS);
-  means_accumulate<NE, NE / 2, NE>(st.u, u, v, ice, st.n_u, st.n_ui, lane, sums + PFT_MEAN_U * PFT_XSUM_WORDS,
-                                   sums + PFT_MEAN_U_ICE * PFT_XSUM_WORDS);
-  means_accumulate<NE, NE / 2, NE>(st.p, p, v, pore, st.n_p, st.n_pp, lane, sums + PFT_MEAN_P * PFT_XSUM_WORDS,
-                                   sums + PFT_MEAN_P_PORE * PFT_XSUM_WORDS);
-}
-
-// rec: the slab's record (written by means_total_kernel), then one record per interior plane
-__global__ __launch_bounds__(PFT_DBLOCK) void means_kernel(const double* __restrict__ fu, const double* __restrict__ fp,
-                                                           const double* __restrict__ fg, int plane, int head, int n3,
-                                                           int segs, int seg_len, double p_thr, double gl_thr,
-                                                           unsigned long long* __restrict__ rec)
-{
-  __shared__ unsigned long long s_rec[PFT_MEANS_REC];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  for (int i = threadIdx.x; i < PFT_MEANS_REC; i += PFT_DBLOCK) s_rec[i] = 0;
-  __syncthreads();
-  MeansState st;
-  st.u.a0 = st.u.a1 = st.u.a2 = st.u.m0 = st.u.m1 = st.u.m2 = 0;
-  st.p.a0 = st.p.a1 = st.p.a2 = st.p.m0 = st.p.m1 = st.p.m2 = 0;
-  st.u.cur = 32;
-  st.p.cur = 31;
-  const long items = (long)n3 * segs;
-  for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    const int k = (int)(item / segs), j = (int)(item - (long)k * segs);
-    const int first = j * seg_len;                                    // within the plane
-    const int len = plane - first < seg_len ? plane - first : seg_len;
-    const long a = (long)k * plane + first;                           // within the run of n3 planes
-    // the frame: elements r = 0 .. span - 1 stand for e_base + r of the run, e_base on a 16-byte
-    // boundary at or one below a; of them [r_lo, r_hi) are the item's (nothing else is read)
-    const long e_base = 2 * ((a + head) >> 1) - head;
-    const int r_lo = (int)(a - e_base), r_hi = r_lo + len;
-    const int span = (r_hi + 1) & ~1;
-    const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
-    const double* wp = fp + e_base;
-    const double* wg = fg + e_base;
-    st.n_u = st.n_p = st.n_ui = st.n_pp = 0;
-    for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
-      if (r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi)
-        means_iter<true>(st, wu, wp, wg, r0, r_lo, r_hi, lane, p_thr, gl_thr, s_rec);
-      else
-        means_iter<false>(st, wu, wp, wg, r0, r_lo, r_hi, lane, p_thr, gl_thr, s_rec);
-    }
-    unsigned long long* sums = s_rec + PFT_MEAN_COUNT;
-    means_flush(st.u, lane, sums + PFT_MEAN_U * PFT_XSUM_WORDS, sums + PFT_MEAN_U_ICE * PFT_XSUM_WORDS);
-    means_flush(st.p, lane, sums + PFT_MEAN_P * PFT_XSUM_WORDS, sums + PFT_MEAN_P_PORE * PFT_XSUM_WORDS);
-    if (lane == 0) {
-      if (st.n_u) atomicAdd(&s_rec[PFT_MEAN_U], st.n_u);
-      if (st.n_p) atomicAdd(&s_rec[PFT_MEAN_P], st.n_p);
-      if (st.n_ui) atomicAdd(&s_rec[PFT_MEAN_U_ICE], st.n_ui);
-      if (st.n_pp) atomicAdd(&s_rec[PFT_MEAN_P_PORE], st.n_pp);
-    }
-    __syncthreads();
-    // one thread per word: the non-zero ones to the plane's record, and the LDS copy zeroed again
-    unsigned long long* dst = rec + (size_t)(k + 1) * PFT_MEANS_REC;
-    for (int i = threadIdx.x; i < PFT_MEANS_REC; i += PFT_DBLOCK) {
-      const unsigned long long x = s_rec[i];
-      if (x) {
-        atomicAdd(&dst[i], x);
-        s_rec[i] = 0;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// the slab's record = the word-wise sum of the planes': per word four threads, each a quarter of
-// the planes, then one of them stores the sum (no atomics: nobody else writes record 0)
-__global__ __launch_bounds__(256) void means_total_kernel(unsigned long long* __restrict__ rec, int n3)
-{
-  __shared__ unsigned long long s_part[4][64];
-  const int l = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int w = blockIdx.x * 64 + l;
-  unsigned long long x = 0;
-  if (w < PFT_MEANS_REC)
-    for (int k = q; k < n3; k += 4) x += rec[(size_t)(k + 1) * PFT_MEANS_REC + w];
-  s_part[q][l] = x;
-  __syncthreads();
-  if (q == 0 && w < PFT_MEANS_REC) rec[w] = s_part[0][l] + s_part[1][l] + s_part[2][l] + s_part[3][l];
-}
-
-extern "C" {
-
-int pft_slab_means(pft_slab* s, int buf, const pft_diag_opts* opts, pft_means* total, pft_means* per_plane)
-{
-  if (!s || !total || buf < 0 || buf >= PFT_BUF_COUNT) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_means");
-  const long plane = s->plane, n = (long)s->d.n3 * plane;
-  // (a 64-bit word holds 2^31 digits; the kernel's 32-bit indices within a plane)
-  if (n > 0x7fffffffL || plane > PFT_MEANS_MAX_PLANE) return -2;
-  const size_t bytes = sizeof(pft_means) * ((size_t)s->d.n3 + 1);
-  if (!s->means_dev) HIPCHK(hipMalloc((void**)&s->means_dev, bytes));
-  if (!s->means_host) HIPCHK(hipHostMalloc((void**)&s->means_host, bytes, hipHostMallocDefault));
-  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
-  const double* fu = s->buf[buf] + plane;
-  const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
-  // at most `cap` workgroups (8 per CU), each inside one plane: a plane is cut into as many
-  // segments as the cap allows, each a whole number of workgroup iterations; with fewer workgroups
-  // than planes a workgroup takes several planes in turn
-  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
-  const long wg_elems = 2L * PFT_DIAG_WG_PAIRS;
-  long want = cap / s->d.n3;
-  if (want < 1) want = 1;
-  const long seg_len = ((plane + want - 1) / want + wg_elems - 1) / wg_elems * wg_elems;
-  const long segs = (plane + seg_len - 1) / seg_len;
-  const long items = segs * s->d.n3;
-  const long wgs = items < cap ? items : cap;
-  const double p_thr = opts ? opts->p_thr : 0.5, gl_thr = opts ? opts->gl_thr : 0.5;
-  // no state carries over between calls: every accumulator word is zeroed on the stream first
-  HIPCHK(hipMemsetAsync(s->means_dev, 0, bytes, s->stream));
-  if (s->means_timing) HIPCHK(hipEventRecord(s->ev_means[0], s->stream));
-  means_kernel<<<(unsigned)wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head, s->d.n3,
-                                                            (int)segs, (int)seg_len, p_thr, gl_thr, s->means_dev);
-  HIPCHK(hipGetLastError());
-  means_total_kernel<<<(PFT_MEANS_REC + 63) / 64, 256, 0, s->stream>>>(s->means_dev, s->d.n3);
-  HIPCHK(hipGetLastError());
-  if (s->means_timing) HIPCHK(hipEventRecord(s->ev_means[1], s->stream));
-  const size_t back = per_plane ? bytes : sizeof(pft_means);
-  HIPCHK(hipMemcpyAsync(s->means_host, s->means_dev, back, hipMemcpyDeviceToHost, s->stream));
-  const int rc = slab_wait(s, nullptr, "pft_slab_means");
-  if (rc) return rc;
-  memcpy(total, s->means_host, sizeof(pft_means));
-  if (per_plane) memcpy(per_plane, s->means_host + PFT_MEANS_REC, sizeof(pft_means) * (size_t)s->d.n3);
-  return 0;
-}
-
-int pft_slab_means_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_means[i]) HIPCHK(hipEventCreate(&s->ev_means[i]));
-  s->means_timing = on ? 1 : 0;
-  return 0;
-}
-
-int pft_slab_means_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->means_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_means[0], s->ev_means[1]));
-  *ms = f;
-  return 0;
-}
-
-}  // extern "C"
-
-// kernel flavours: KCACHE (any n1, aux arrays), KFUSED (LDS tile, stage inputs recomputed from x
-// and the K's -- the default for even n1); 1 was the retired LDS-tiled aux-array kernel
-enum { KCACHE = 0, KFUSED = 2 };
-
-// resident workgroups per CU of the kernel launch_kernel would run (hipOccupancy..., cached)
+// resident workgroups per CU of the kernel launch_stage would run (hipOccupancy..., cached)
 template <int STAGE, int MODE, bool GLS>
-static int kernel_occupancy(int kind, int wx)
+static int kernel_occupancy(int kind)
 {
-  static int cache[3] = {0, 0, 0};
-  (void)wx;
-  int& n = cache[kind];
+  static int cache[2] = {0, 0};
+  int& n = cache[kind == KFUSED];
   if (n) return n;
   const void* f = kind == KFUSED ? (const void*)merson_fused<STAGE, MODE, GLS>
                                  : (const void*)merson_stage<STAGE, MODE, GLS>;
@@ -3777,65 +2665,33 @@ static int kernel_occupancy(int kind, int wx)
   return n;
 }
 
-template <int STAGE, bool GLS>
-static int occupancy_mode(int mode, int kind, int wx)
+static int stage_occupancy(int stage, int mode, int gls, int kind)
 {
-  switch (mode) {
-    case 0: return kernel_occupancy<STAGE, 0, GLS>(kind, wx);
-    case 1: return kernel_occupancy<STAGE, 1, GLS>(kind, wx);
-    case 2: return kernel_occupancy<STAGE, 2, GLS>(kind, wx);
-    case 10: return kernel_occupancy<STAGE, 10, GLS>(kind, wx);
-    default: return kernel_occupancy<STAGE, 11, GLS>(kind, wx);
-  }
+  return with_stage(stage, [&](auto st) {
+    return with_mode(mode, [&](auto m) {
+      return with_bool(gls, [&](auto g) {
+        return kernel_occupancy<decltype(st)::value, decltype(m)::value, decltype(g)::value>(kind);
+      });
+    });
+  });
 }
 
-static int stage_occupancy(int stage, int mode, int gls, int kind, int wx)
-{
-  switch (stage) {
-    case 0: return gls ? occupancy_mode<0, true>(mode, kind, wx) : occupancy_mode<0, false>(mode, kind, wx);
-    case 1: return gls ? occupancy_mode<1, true>(mode, kind, wx) : occupancy_mode<1, false>(mode, kind, wx);
-    case 2: return gls ? occupancy_mode<2, true>(mode, kind, wx) : occupancy_mode<2, false>(mode, kind, wx);
-    case 3: return gls ? occupancy_mode<3, true>(mode, kind, wx) : occupancy_mode<3, false>(mode, kind, wx);
-    case 4: return gls ? occupancy_mode<4, true>(mode, kind, wx) : occupancy_mode<4, false>(mode, kind, wx);
-    default: return gls ? occupancy_mode<5, true>(mode, kind, wx) : occupancy_mode<5, false>(mode, kind, wx);
-  }
-}
-
-template <int STAGE, int MODE, bool GLS>
-static void launch_kernel(int kind, int wx, dim3 g, hipStream_t st, const StageArgs& a, const pft_consts& c)
-{
-  if (kind == KFUSED) {
-    merson_fused<STAGE, MODE, GLS><<<g, PFT_FBLOCK, 0, st>>>(a, c);
-  } else {
-    merson_stage<STAGE, MODE, GLS><<<g, PFT_BLOCK, 0, st>>>(a, c);
-  }
-}
-
-template <int STAGE, bool GLS>
-static void launch_mode(int mode, int kind, int wx, dim3 g, hipStream_t st, const StageArgs& a,
-                        const pft_consts& c)
-{
-  switch (mode) {
-    case 0: launch_kernel<STAGE, 0, GLS>(kind, wx, g, st, a, c); break;
-    case 1: launch_kernel<STAGE, 1, GLS>(kind, wx, g, st, a, c); break;
-    case 2: launch_kernel<STAGE, 2, GLS>(kind, wx, g, st, a, c); break;
-    case 10: launch_kernel<STAGE, 10, GLS>(kind, wx, g, st, a, c); break;
-    case 11: launch_kernel<STAGE, 11, GLS>(kind, wx, g, st, a, c); break;
-  }
-}
-
-template <bool GLS>
-static void launch_stage(int stage, int mode, int kind, int wx, dim3 g, hipStream_t st, const StageArgs& a,
+static void launch_stage(int stage, int mode, int gls, int kind, dim3 g, hipStream_t st, const StageArgs& a,
                          const pft_consts& c)
 {
-  switch (stage) {
-    case 0: launch_mode<0, GLS>(mode, kind, wx, g, st, a, c); break;
-    case 1: launch_mode<1, GLS>(mode, kind, wx, g, st, a, c); break;
-    case 2: launch_mode<2, GLS>(mode, kind, wx, g, st, a, c); break;
-    case 3: launch_mode<3, GLS>(mode, kind, wx, g, st, a, c); break;
-    case 4: launch_mode<4, GLS>(mode, kind, wx, g, st, a, c); break;
-    case 5: launch_mode<5, GLS>(mode, kind, wx, g, st, a, c); break;
-  }
+  with_stage(stage, [&](auto sv) {
+    with_mode(mode, [&](auto mv) {
+      with_bool(gls, [&](auto gv) {
+        constexpr int STAGE = decltype(sv)::value, MODE = decltype(mv)::value;
+        constexpr bool GLS = decltype(gv)::value;
+        if (kind == KFUSED) {
+          merson_fused<STAGE, MODE, GLS><<<g, PFT_FBLOCK, 0, st>>>(a, c);
+        } else {
+          merson_stage<STAGE, MODE, GLS><<<g, PFT_BLOCK, 0, st>>>(a, c);
+        }
+      });
+    });
+  });
 }
 
 extern "C" {
@@ -3968,7 +2824,7 @@ int pft_slab_tile_geometry(const pft_slab* s, int stage, int* wx, int* ty)
   if (kind == KCACHE) {
     *wx = 0;
     *ty = 0;
-  } else if (kind == KFUSED && auto_tile) {
+  } else if (auto_tile) {
     slab_fgeo(s, wx, ty);
   } else {
     *wx = s->tile_wx;
@@ -4071,10 +2927,8 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
   a.has_above = s->d.has_above;
   a.k_begin = k_begin;
   a.k_end = k_end;
-  // tile width: 1 = per stage (measured at 400^3: the VALU-bound stages 0-2 run faster on 32x16
-  // tiles -- fewer idle lanes at the x edge, 200 = 6.25 x 32 -- the HBM-bound stages 3-5 on 64x8)
+  // tile: tile_wx 1 / 2 = automatic (fused_geometry), else that many pairs per row
   const bool auto_tile = s->tile_wx == 1 || s->tile_wx == 2;
-  const int wx = kind == KCACHE ? 0 : auto_tile ? (stage <= 2 ? 16 : 32) : s->tile_wx;
   if (kind == KFUSED) {
     if (auto_tile) {
       slab_fgeo(s, &a.gwx, &a.gty);
@@ -4084,15 +2938,12 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
     }
     if (!fused_geometry_ok(a.gwx, a.gty)) return -2;
     a.ntile = ((s->d.n1 + 2 * a.gwx - 1) / (2 * a.gwx)) * ((s->d.n2 + a.gty - 1) / a.gty);
-  } else if (wx) {
-    const int TX = 2 * wx, TY = PFT_BLOCK / wx;
-    a.ntile = ((s->d.n1 + TX - 1) / TX) * ((s->d.n2 + TY - 1) / TY);
   } else {
     a.ntile = (s->plane + PFT_BLOCK - 1) / PFT_BLOCK;
   }
   if (ends) {
     const int n3 = s->d.n3;
-    const int occ = stage_occupancy(stage, mode, gls, kind, wx);
+    const int occ = stage_occupancy(stage, mode, gls, kind);
     const int kz = s->kz > 0 ? s->kz : chunk_kz(s, 14, occ, a.ntile, n3, 3);
     const int nch = (n3 + kz - 1) / kz;
     if (kz < 2 || nch < 3 || n3 - (nch - 1) * kz < 2) ends = false;
@@ -4107,7 +2958,7 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
   if (s->kz > 0) {
     a.kz = s->kz;
   } else if (ends) {
-    a.kz = chunk_kz(s, 14, stage_occupancy(stage, mode, gls, kind, wx), a.ntile, nplanes, 3);
+    a.kz = chunk_kz(s, 14, stage_occupancy(stage, mode, gls, kind), a.ntile, nplanes, 3);
   } else {
     // automatic (chunk_kz)
     // Measured at 400^3 (80 tiles):
@@ -4115,7 +2966,7 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
     // 0.153 vs 0.163 for 9 of 45.  On a 400 x 400 x 100 slab (320 tiles, one 800^3 8-way rank)
     // stages 4-5: 3 chunks (960 workgroups, 2 rounds) 0.261 / 0.349 ms against 0.314 / 0.436 for
     // one round of 320 (64 CUs with 2 workgroups, 192 with 1).
-    const int occ = stage_occupancy(stage, mode, gls, kind, wx);
+    const int occ = stage_occupancy(stage, mode, gls, kind);
     a.kz = chunk_kz(s, stage + 6 * (gls ? 1 : 0), occ, a.ntile, nplanes);
   }
   a.nchunk = (nplanes + a.kz - 1) / a.kz;
@@ -4223,10 +3074,7 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
     HIPCHK(hipStreamWaitEvent(s->bnd, s->ev_pre, 0));
     st = s->bnd;
   }
-  if (gls)
-    launch_stage<true>(stage, mode, kind, wx, g, st, a, s->c);
-  else
-    launch_stage<false>(stage, mode, kind, wx, g, st, a, s->c);
+  launch_stage(stage, mode, gls, kind, g, st, a, s->c);
   HIPCHK(hipGetLastError());
   if (beside) {
     HIPCHK(hipEventRecord(s->ev_bnd, s->bnd));
@@ -4774,40 +3622,43 @@ int pft_slab_stage_spec(pft_slab* s, double t_stage, int k_begin, int k_end)
 
 // ---- pair kernels (merson_pair): stages 2+3 and 4+5 of a step, one launch each -------------
 
-template <int SA, bool GLX, int LWP>
-static void launch_pair_lwp(int mode, dim3 g, hipStream_t st, const PairArgs& a, const pft_consts& c)
+static void launch_pair(int first, int mode, bool glx, int lwp, dim3 g, hipStream_t st, const PairArgs& a,
+                        const pft_consts& c)
 {
-  switch (mode) {
-    case 0: merson_pair<SA, 0, GLX, LWP><<<g, PFT_PBLOCK, 0, st>>>(a, c); break;
-    case 1: merson_pair<SA, 1, GLX, LWP><<<g, PFT_PBLOCK, 0, st>>>(a, c); break;
-    case 2: merson_pair<SA, 2, GLX, LWP><<<g, PFT_PBLOCK, 0, st>>>(a, c); break;
-    case 10: merson_pair<SA, 10, GLX, LWP><<<g, PFT_PBLOCK, 0, st>>>(a, c); break;
-    case 11: merson_pair<SA, 11, GLX, LWP><<<g, PFT_PBLOCK, 0, st>>>(a, c); break;
-  }
+  with_bool(first == 2, [&](auto fv) {
+    with_mode(mode, [&](auto mv) {
+      with_bool(glx, [&](auto gv) {
+        with_bool(lwp == 12, [&](auto lv) {
+          constexpr int SA = decltype(fv)::value ? 2 : 4, MODE = decltype(mv)::value;
+          constexpr int LWP = decltype(lv)::value ? 12 : 22;
+          constexpr bool GLX = decltype(gv)::value;
+          merson_pair<SA, MODE, GLX, LWP><<<g, PFT_PBLOCK, 0, st>>>(a, c);
+        });
+      });
+    });
+  });
 }
 
-template <int SA, bool GLX>
-static void launch_pair_mode(int mode, int lwp, dim3 g, hipStream_t st, const PairArgs& a, const pft_consts& c)
+// resident workgroups per CU of a pair kernel (hipOccupancy..., cached; the 22-pair pitch's, gl
+// from its own input)
+template <int SA, int MODE>
+static int pair_kernel_occupancy()
 {
-  if (lwp == 12) launch_pair_lwp<SA, GLX, 12>(mode, g, st, a, c);
-  else launch_pair_lwp<SA, GLX, 22>(mode, g, st, a, c);
-}
-
-template <int SA, bool GLX>
-static int pair_occupancy_mode(int mode)
-{
-  static int cache[12] = {0};
-  int& n = cache[mode];
+  static int n = 0;
   if (n) return n;
-  const void* f = mode == 0 ? (const void*)merson_pair<SA, 0, GLX, 22>
-                : mode == 1 ? (const void*)merson_pair<SA, 1, GLX, 22>
-                : mode == 2 ? (const void*)merson_pair<SA, 2, GLX, 22>
-                : mode == 10 ? (const void*)merson_pair<SA, 10, GLX, 22>
-                             : (const void*)merson_pair<SA, 11, GLX, 22>;
   int b = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, f, PFT_PBLOCK, 0) != hipSuccess || b < 1) b = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)merson_pair<SA, MODE, false, 22>, PFT_PBLOCK, 0) != hipSuccess || b < 1) b = 1;
   n = b;
   return n;
+}
+
+static int pair_occupancy(int first, int mode)
+{
+  return with_bool(first == 2, [&](auto fv) {
+    return with_mode(mode, [&](auto mv) {
+      return pair_kernel_occupancy<decltype(fv)::value ? 2 : 4, decltype(mv)::value>();
+    });
+  });
 }
 
 // the LDS row pitch (pairs) of a pair tile tx cells wide: 12 up to 20 cells, 22 up to 40
@@ -4911,7 +3762,7 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
     // the first and the last chunk must hold the two planes at each end (kz >= 2, a last chunk of
     // two planes or more) and leave a chunk between them; otherwise the two-plane boundary chunks
     const int n3 = s->d.n3;
-    const int occ = first == 2 ? pair_occupancy_mode<2, false>(mode) : pair_occupancy_mode<4, false>(mode);
+    const int occ = pair_occupancy(first, mode);
     const int kz = s->kz > 0 ? s->kz : chunk_kz(s, 14 + (first == 4 ? 1 : 0), occ, s->pair_ntile, n3, 3);
     const int nch = (n3 + kz - 1) / kz;
     if (kz < 2 || nch < 3 || n3 - (nch - 1) * kz < 2) ends = false;
@@ -4938,7 +3789,7 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
   } else {
     // z-chunks as run_stage's cost model: a chunk of kz planes evaluates stage A on kz + 2 and
     // loads kz + 3; `occ` workgroups per CU (one: 141 KiB of LDS)
-    const int occ = first == 2 ? pair_occupancy_mode<2, false>(mode) : pair_occupancy_mode<4, false>(mode);
+    const int occ = pair_occupancy(first, mode);
     // end chunks first: at least three chunks, so that the first and last of a column are done
     // while the others still run (the exchange's copies go beside them)
     a.kz = chunk_kz(s, (ends ? 14 : 12) + (first == 4 ? 1 : 0), occ, a.ntile, nplanes, ends ? 3 : 1);
@@ -5026,13 +3877,7 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
     st = s->bnd;
   }
   const int lwp = pair_lwp(a.tx);
-  if (first == 2) {
-    if (glx) launch_pair_mode<2, true>(mode, lwp, g, st, a, s->c);
-    else launch_pair_mode<2, false>(mode, lwp, g, st, a, s->c);
-  } else {
-    if (glx) launch_pair_mode<4, true>(mode, lwp, g, st, a, s->c);
-    else launch_pair_mode<4, false>(mode, lwp, g, st, a, s->c);
-  }
+  launch_pair(first, mode, glx, lwp, g, st, a, s->c);
   HIPCHK(hipGetLastError());
   if (beside) {
     HIPCHK(hipEventRecord(s->ev_bnd, s->bnd));

@@ -1,7 +1,7 @@
 /*
  * pft_means.c -- f6: the exact accumulator and the means record on a host array
  * (include/pft_means.h): the host-layout twin of the device reduction (means_kernel,
- * pft_kernels.hip), which must give the same raw words.
+ * pft_reduce.hip), which must give the same raw words.
  *
  * Host C99 (with the compiler's 128-bit integer), OpenMP over the planes like pft_diag_host.
  * Every word is a sum of integers, so the threads' records merge to the same bits in any order.
