@@ -22,6 +22,7 @@
 
 #include "pft_diag.h"
 #include "pft_means.h"
+#include "pft_io.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -205,6 +206,25 @@ int pft_slab_snapshot_export(pft_slab * s, int buf, int link, void ** image);
 /* HIP-event timing of the export kernel alone (scripts/snapshot_time.py), as pft_slab_diag_timing */
 int pft_slab_snapshot_timing(pft_slab * s, int on);
 int pft_slab_snapshot_last_ms(pft_slab * s, double * ms);
+
+/* f11: the *region image* of buffer `buf` (pft_io.h; host twin pft_region_image_host): the selected
+   cells of u, p, gl in turn as big-endian words, dense, [k][j][i] with i fastest.  r_local is the
+   region with its k triple already slab-local: (klocal, kcount, stride[2]) of pft_region_local;
+   count[2] == 0 (a slab that owns none of the region) moves nothing and succeeds; -2 for a region
+   that leaves the slab's interior.  region_kernel on the compute stream, ordered after everything
+   queued there, blockIdx.y the field: a lane moves one word per trip of a grid-stride loop -- one
+   8-byte load from the strided box, a 64-bit integer byte swap, one 8-byte store -- so the stores
+   are dense for every region and the loads are coalesced when stride[0] == 1; no LDS, no atomics,
+   no ghost plane.  The slab's whole interior at stride 1 goes to the f7 export instead.  Env
+   PFT_REGION_WGS=n (read at pft_slab_create) caps the kernel's workgroups (default 8 per CU, as the
+   f7 export; tests).  export_region_be: dst is 8-byte aligned device or host-mapped memory; the
+   wait is the slab's bounded one and a poisoned slab refuses, as in pft_slab_export_be.
+   region_export: through the slab's pinned image buffer (a region image never exceeds the full
+   image), by either host link, after pft_snapshot_writer_release of the buffer's previous image.
+   pft_slab_snapshot_timing / _last_ms cover this kernel too. */
+size_t pft_slab_region_image_bytes(const pft_region * r_local);
+int pft_slab_export_region_be(pft_slab * s, int buf, const pft_region * r_local, void * dst);
+int pft_slab_region_export(pft_slab * s, int buf, const pft_region * r_local, int link, void ** image);
 
 /* One Merson stage (stage 1..5) as ONE fused kernel: K = f(stage input) and the pointwise stage
    combine of RK_MPI_SAsolver_hybrid2.c:378-450 (stage 5: error norm :507-524 and the candidate

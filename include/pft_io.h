@@ -89,6 +89,40 @@ int pft_snapshot_writer_release(const void * image);
 int pft_snapshot_writer_wait(void);
 int pft_snapshot_writer_shutdown(void);
 
+/* f11: a *region* of the grid -- per axis the global interior indices start + m*stride, m = 0 ..
+   count-1 ([0] = i of n1, [1] = j of n2, [2] = k of total_n3; every stride and count at least 1,
+   the last index inside the grid) -- and its dataset: a snapshot dataset of the selected cells
+   alone.  Dimensions n3, n2, n1 = the counts; the coordinate variables are the full dataset's
+   entries at the selected indices, bit for bit; the global attributes are a full dataset's, in
+   its order, followed by three int[3] attributes region_start, region_count, region_stride in
+   (i, j, k) order; CDF-1 / CDF-2 by the rule of pft_snapshot_create.  A full dataset is unchanged.
+     region_check   0, or -2 for a region that breaks a rule above;
+     region_local   this slab's share of the region's k axis: *kfirst the index within that axis
+                    of the first selected plane the slab owns, *kcount how many it owns (0: none;
+                    then *kfirst is where they would lie and *klocal is 0), *klocal the slab-local
+                    plane (0-based) of the first one;
+     region_image_bytes / region_image_host   the region image of a slab, the host twin of
+                    pft_slab_export_region_be: for q = u, p, gl in turn its kcount * count[1] *
+                    count[0] selected doubles as big-endian words, [k][j][i] with i fastest;
+     create_region / region_ranges   the dataset's header and coordinates, and the three places
+                    of this slab's region image in it (bytes 0 for a slab that owns none; -4 when
+                    the dataset's dimensions are not the region's counts).
+   write_image, write_image_async and read_image take these ranges as they take a slab's; ranges of
+   0 bytes move nothing and succeed.  As a restart a region dataset is refused by its dimensions
+   (-4), unless it selects the whole grid. */
+typedef struct { int start[3], count[3], stride[3]; } pft_region;   /* [0] = i (n1), [1] = j (n2), [2] = k (total_n3) */
+int pft_region_check(const pft_grid * g, const pft_region * r);
+int pft_region_local(const pft_grid * g, const pft_region * r, int * kfirst, int * kcount, int * klocal);
+size_t pft_region_image_bytes(const pft_grid * g, const pft_region * r);
+int pft_region_image_host(const pft_grid * g, const pft_region * r, const double * x_padded, void * out);
+int pft_snapshot_create_region(const char * path, const pft_grid * g, const pft_region * r, const double * param,
+                               const pft_snapshot_info * info, int version);
+int pft_snapshot_region_ranges(const char * path, const pft_grid * g, const pft_region * r, pft_snapshot_ranges * ranges);
+/* the host path, as pft_snapshot_write: create_region (rank 0) + barrier + every rank's region
+   image of the host padded array x into its ranges, over the current communicator */
+int pft_snapshot_write_region(const char * path, const pft_grid * g, const pft_region * r, const double * param,
+                              const pft_snapshot_info * info, const double * x, int version);
+
 /* the title the reference writes (:1129, :2405): "Intertrack simulation (%s). Time: %g" */
 int pft_snapshot_title(char * buf, int size, const char * comment, double t);
 

@@ -96,6 +96,22 @@ int pft_solver_ic_formulas_device(int nprog, const int * qs, const int * lens, c
 #define PFT_SNAP_LINK_DEFAULT PFT_SNAP_LINK_STAGED
 int pft_solver_snapshot_write(const char * path, const double * param, const pft_snapshot_info * info, int flags);
 int pft_solver_snapshot_wait(void);
+/* f11: a region dataset (pft_io.h: pft_region, pft_snapshot_create_region) of the device-resident
+   x: the flags, the validity rules and the codes of pft_solver_snapshot_write (-3 without a
+   resident state, nothing created; -2 from a Service_Callback with several ranks), and -2 on every
+   rank for a bad region, before any file or device work.  Collective: rank 0 writes the header
+   even when its slab owns no selected plane, the status allreduce is the barrier, every rank
+   exports its share (pft_region_local, pft_slab_region_export) and hands it to the background
+   writer; a rank that owns none takes part in every collective and queues no write.
+   pft_solver_snapshot_wait covers these writes.
+   pft_solver_region: this rank's share of the region (kcount * count[1] * count[0] doubles per
+   field, u, p, gl in turn; pft_region_image_bytes of the slab's grid) into out_native in the
+   host's byte order, no file: the region image through the pinned buffer, swapped back on the
+   host.  Not collective.  The same validity rules; out_native may be NULL when the share is
+   empty. */
+int pft_solver_snapshot_region_write(const char * path, const double * param, const pft_snapshot_info * info,
+                                     const pft_region * region, int flags);
+int pft_solver_region(const pft_region * region, double * out_native);
 /* f7 (after RK_MPI_SA_init): the state of a snapshot dataset read on the device, as a restart
    (icond_file, intertrack.c:2023-2117): each rank preads only its own planes -- no distribution
    through a master -- and imports them into X and XN (pft_slab_import_be); then exactly the end of

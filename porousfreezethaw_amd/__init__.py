@@ -84,6 +84,16 @@ class pft_snapshot_ranges(C.Structure):
     _fields_ = [("off", C.c_ulonglong * 3), ("bytes", C.c_ulonglong)]
 
 
+class pft_region(C.Structure):
+    """include/pft_io.h: per axis start, count, stride in global interior indices; [0] = i, [1] = j, [2] = k"""
+    _fields_ = [("start", C.c_int * 3), ("count", C.c_int * 3), ("stride", C.c_int * 3)]
+
+    def selection(self):
+        """the numpy index of the region in a [k, j, i] array: three slices"""
+        return tuple(slice(self.start[a], self.start[a] + (self.count[a] - 1) * self.stride[a] + 1, self.stride[a])
+                     for a in (2, 1, 0))
+
+
 class pft_solver_stats(C.Structure):
     _fields_ = [("path", C.c_int), ("nprocs", C.c_int), ("rank", C.c_int),
                 ("kernel_launches", C.c_long), ("steps_total", C.c_long), ("last_eps", C.c_double),
@@ -273,6 +283,21 @@ def lib():
         L.pft_solver_snapshot_write.argtypes = [C.c_char_p, dp, sp, C.c_int]
         L.pft_solver_snapshot_read.argtypes = [C.c_char_p]
         L.pft_comm_size.argtypes = [C.c_void_p]
+        gnp = C.POINTER(pft_region)
+        L.pft_region_check.argtypes = [gp, gnp]
+        L.pft_region_local.argtypes = [gp, gnp, ip, ip, ip]
+        L.pft_region_image_bytes.argtypes = [gp, gnp]
+        L.pft_region_image_bytes.restype = C.c_size_t
+        L.pft_region_image_host.argtypes = [gp, gnp, dp, C.c_void_p]
+        L.pft_snapshot_create_region.argtypes = [C.c_char_p, gp, gnp, dp, sp, C.c_int]
+        L.pft_snapshot_region_ranges.argtypes = [C.c_char_p, gp, gnp, rp]
+        L.pft_snapshot_write_region.argtypes = [C.c_char_p, gp, gnp, dp, sp, dp, C.c_int]
+        L.pft_slab_region_image_bytes.argtypes = [gnp]
+        L.pft_slab_region_image_bytes.restype = C.c_size_t
+        L.pft_slab_export_region_be.argtypes = [C.c_void_p, C.c_int, gnp, C.c_void_p]
+        L.pft_slab_region_export.argtypes = [C.c_void_p, C.c_int, gnp, C.c_int, vpp]
+        L.pft_solver_snapshot_region_write.argtypes = [C.c_char_p, dp, sp, gnp, C.c_int]
+        L.pft_solver_region.argtypes = [gnp, dp]
         _lib = L
     return _lib
 
@@ -313,6 +338,34 @@ def comm_init_ipc(nranks, rank, name, device=0):
 def comm_destroy(c):
     lib().pft_comm_set_current(None)
     lib().pft_comm_destroy(c)
+
+
+def region(k, j, i, grid):
+    """The pft_region (include/pft_io.h) of a selection given the way numpy indexes interior()'s
+    [k, j, i] axes on the whole grid: each of k, j, i a slice or an int.  An int n is the single
+    index n (negative: from the end), and that axis is kept with length 1.  A slice is normalised
+    with slice.indices, as numpy does.  grid: a pft_grid, or (total_n3, n2, n1).  ValueError for a
+    step that is not positive, an empty axis and an int past the grid -- before any device work."""
+    dims = (grid.total_n3, grid.n2, grid.n1) if isinstance(grid, pft_grid) else tuple(int(v) for v in grid)
+    r = pft_region()
+    for axis, (name, sel, n) in enumerate(zip("kji", (k, j, i), dims)):
+        if isinstance(sel, slice):
+            start, stop, step = sel.indices(n)       # (a zero step: slice.indices' own ValueError)
+            if step < 1:
+                raise ValueError(f"region: the step of {name} must be positive, not {step}")
+            count = len(range(start, stop, step))
+            if count < 1:
+                raise ValueError(f"region: the selection {sel} of {name} is empty on {n} cells")
+        else:
+            try:
+                start = sel.__index__()
+            except AttributeError:
+                raise ValueError(f"region: {name} must be a slice or an int, not {sel!r}") from None
+            if not -n <= start < n:
+                raise ValueError(f"region: index {sel} of {name} lies past the grid's {n} cells")
+            start, step, count = start % n, 1, 1
+        r.start[2 - axis], r.count[2 - axis], r.stride[2 - axis] = start, count, step
+    return r
 
 
 def params_array(values):
@@ -375,6 +428,13 @@ class Simulation:
                              "solver: it cannot be combined with initial= or init_solver=False")
         L1, L2, L3 = L
         self.lib = L_ = lib()
+        if icond_file is not None:
+            # the dataset's dimensions before any solver work: a region dataset, say (-4, the code
+            # pft_solver_snapshot_read itself gives when it is asked)
+            f1, f2, f3 = read_snapshot_info(icond_file)[:3]
+            if (f1, f2, f3) != (n1, n2, total_n3):
+                raise OSError(f"icond_file {icond_file}: the dataset's dimensions {f1}x{f2}x{f3} differ from the "
+                              f"grid's {n1}x{n2}x{total_n3} (-4)")
         self.grid = pft_grid()
         rc = L_.pft_grid_init(C.byref(self.grid), n1, n2, total_n3, nprocs, rank, L1, L2, L3, calc_mode)
         if rc:
@@ -659,32 +719,89 @@ class Simulation:
         return d
 
     # -- f7: snapshots from the resident state -----------------------------------------------------
-    def snapshot_device(self, path, info, wait=True, version=0, link=None):
+    def _region(self, sel):
+        """the pft_region of a selection (region()) on this simulation's grid; a pft_region is checked"""
+        if isinstance(sel, pft_region):
+            if self.lib.pft_region_check(C.byref(self.grid), C.byref(sel)):
+                raise ValueError("region: the pft_region does not lie inside the grid")
+            return sel
+        try:
+            k, j, i = sel
+        except (TypeError, ValueError):
+            raise ValueError(f"region: three items (k, j, i), each a slice or an int, not {sel!r}") from None
+        return region(k, j, i, self.grid)
+
+    def region_share(self, sel):
+        """(kfirst, kcount, klocal) of pft_region_local: this slab's share of the region's k axis"""
+        r, a, b, c = self._region(sel), C.c_int(), C.c_int(), C.c_int()
+        rc = self.lib.pft_region_local(C.byref(self.grid), C.byref(r), C.byref(a), C.byref(b), C.byref(c))
+        if rc:
+            raise ValueError(f"pft_region_local failed ({rc})")
+        return a.value, b.value, c.value
+
+    def region(self, sel, where="device"):
+        """f11: this rank's share of a region of the state, float64 [3][c3'][c2][c1] -- what
+        interior()[:, k, j, i] holds for the slab's planes, ints kept as axes of length 1 (sel: see
+        region()).  where="device": gathered on the device from the resident state
+        (pft_solver_region: the region image through pinned memory, no file, no download of the
+        rest); RuntimeError when nothing is resident.  where="host": the same from self.x."""
+        if where not in ("device", "host"):
+            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
+        r = self._region(sel)
+        _, kcount, klocal = self.region_share(r)
+        out = np.zeros((3, kcount, r.count[1], r.count[0]))
+        if where == "host":
+            g = self.grid
+            ks = slice(2 + klocal, 2 + klocal + kcount * r.stride[2], r.stride[2])
+            js = slice(2 + r.start[1], 2 + r.start[1] + r.count[1] * r.stride[1], r.stride[1])
+            is_ = slice(2 + r.start[0], 2 + r.start[0] + r.count[0] * r.stride[0], r.stride[0])
+            out[...] = self.padded()[:, ks, js, is_][:, :kcount, :r.count[1], :r.count[0]]
+            return out
+        rc = self.lib.pft_solver_region(C.byref(r), _dp(out))
+        if rc == -3:
+            raise RuntimeError("region: no state is resident on the device (no initialised solver, or no fused "
+                               "solve or device IC yet)")
+        if rc:
+            raise OSError(f"pft_solver_region failed ({rc}): {self.lib.pft_hip_last_error()}")
+        return out
+
+    def snapshot_device(self, path, info, wait=True, version=0, link=None, region=None):
         """Write the device-resident state as the snapshot dataset `path` (info: snapshot_info())
         without a download: the slab's image is byte-swapped on the device into pinned host memory
         and written by the library's background thread (pft_solver_snapshot_write; collective on
         several ranks).  wait=False returns once the image has left the device -- the next solve may
         run while the file is written; snapshot_wait() (or close()) then ends the write and reports
         its errors.  version: 0 automatic, 1 CDF-1, 2 CDF-2.  link: None (the default host link),
-        "direct" or "staged".  RuntimeError when nothing is resident (no file is created)."""
+        "direct" or "staged".  RuntimeError when nothing is resident (no file is created).
+        region=sel (f11; see region()): the dataset of the selected cells alone -- the same variables,
+        attributes and coordinate variables, only smaller, plus the region_start / region_count /
+        region_stride attributes -- gathered on the device: only the selection crosses to the host."""
         if link not in (None, "direct", "staged"):
             raise ValueError(f"link must be None, 'direct' or 'staged', not {link!r}")
         if version not in (0, 1, 2):
             raise ValueError(f"version must be 0, 1 or 2, not {version!r}")
         flags = (0 if wait else PFT_SNAP_ASYNC) | (version << 8)
         flags |= {None: 0, "direct": PFT_SNAP_DIRECT, "staged": PFT_SNAP_STAGED}[link]
-        if not self._snapshot_device(path, info, flags):
+        if region is not None:
+            region = self._region(region)
+        if not self._snapshot_device(path, info, flags, region):
             raise RuntimeError("snapshot_device: no state is resident on the device (no initialised solver, or "
                                "no fused solve or device IC yet)")
 
-    def _snapshot_device(self, path, info, flags):
+    def _snapshot_device(self, path, info, flags, region=None):
         """snapshot_device(); False when nothing is resident (pft_solver_snapshot_write's -3, the same
-        on every rank, and no file)"""
-        rc = self.lib.pft_solver_snapshot_write(os.fsencode(path), _dp(self.params), C.byref(info), flags)
+        on every rank, and no file); region: a pft_region or None"""
+        if region is None:
+            what = "pft_solver_snapshot_write"
+            rc = self.lib.pft_solver_snapshot_write(os.fsencode(path), _dp(self.params), C.byref(info), flags)
+        else:
+            what = "pft_solver_snapshot_region_write"
+            rc = self.lib.pft_solver_snapshot_region_write(os.fsencode(path), _dp(self.params), C.byref(info),
+                                                           C.byref(region), flags)
         if rc == -3:
             return False
         if rc:
-            raise OSError(f"pft_solver_snapshot_write({path}) failed ({rc}): {self.lib.pft_hip_last_error()}")
+            raise OSError(f"{what}({path}) failed ({rc}): {self.lib.pft_hip_last_error()}")
         if flags & PFT_SNAP_ASYNC:
             self._snap_pending = True
         return True
@@ -699,7 +816,8 @@ class Simulation:
 
     def run_series(self, final_time=None, saved_files=None, times=None, snapshot_path=None, comment="",
                    diag=True, opts=None, means=False, snapshot_where="host", snapshot_async=False,
-                   first_snapshot=0, total_snapshots=None, skip_first=False):
+                   first_snapshot=0, total_snapshots=None, skip_first=False, regions=None, region_every=1,
+                   snapshot_full=True):
         """The driver's snapshot loop (intertrack.c:2265-2283).  Snapshot 0 is the state as it
         stands (no solve); snapshot s solves to series_times(t0, final_time, saved_files)[s], or
         to times[s - 1] when times= lists the solve targets.  The steps run device-resident
@@ -718,7 +836,17 @@ class Simulation:
         intertrack.c:1642-1669, 2265-2271): the state as it stands is snapshot k of saved_files,
         rows and file names are numbered from k and the targets are series_times(..., first=k);
         snapshot k is written again unless skip_first (:2315).  total_snapshots: the files'
-        attribute when times= is given (default: first_snapshot + the number of rows)."""
+        attribute when times= is given (default: first_snapshot + the number of rows).
+        regions={"xz": sel, ...} (f11; sel: see region()): each named region is written as the region
+        dataset "<snapshot_path>.<name>.%03d.ncd" at every snapshot whose number is a multiple of
+        region_every, by the route of snapshot_where and snapshot_async; snapshot_full=False leaves
+        the full datasets out altogether.  The rows do not depend on any of it."""
+        region_every = int(region_every)
+        if region_every < 1:
+            raise ValueError(f"region_every must be at least 1, not {region_every}")
+        if regions and snapshot_path is None:
+            raise ValueError("regions= needs snapshot_path")
+        regions = {str(name): self._region(sel) for name, sel in (regions or {}).items()}
         if snapshot_where not in ("host", "device"):
             raise ValueError(f"snapshot_where must be 'host' or 'device', not {snapshot_where!r}")
         if snapshot_async and snapshot_where != "device":
@@ -739,14 +867,14 @@ class Simulation:
         rows = []
         try:
             rows = self._run_series(targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
-                                    snapshot_where, snapshot_async, skip_first)
+                                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full)
         finally:
             if self._snap_pending:
                 self.snapshot_wait()
         return rows
 
     def _run_series(self, targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
-                    snapshot_where, snapshot_async, skip_first):
+                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full):
         rows = []
         for s, T in enumerate(targets, first):
             rc = None
@@ -774,19 +902,25 @@ class Simulation:
             if snapshot_path is not None and not (s == first and skip_first):
                 info = snapshot_info(self.system.t, self.system.h, end, self.system.delta, self.grid.calc_mode,
                                      snapshot=s, total_snapshots=total, comment=comment)
-                name = "%s.%03d.ncd" % (snapshot_path, s)
-                written = False
-                if snapshot_where == "device":
-                    written = self._snapshot_device(name, info, PFT_SNAP_ASYNC if snapshot_async else 0)
-                    if not written and s != first:
-                        raise RuntimeError("run_series: no state is resident on the device after the solve "
-                                           "(the host-staged path keeps none)")
-                if not written:
-                    # the host path; with "device" the first snapshot of a host IC, not yet resident
-                    drc = self.lib.pft_solver_download(C.byref(self.system))
-                    if drc and not (drc == -2 and s == first):   # -2 at the first: a host IC, nothing resident yet
-                        raise RuntimeError(f"pft_solver_download failed ({drc})")
-                    save_snapshot(self, name, info)
+                files = [("%s.%03d.ncd" % (snapshot_path, s), None)] if snapshot_full else []
+                if s % region_every == 0:
+                    files += [("%s.%s.%03d.ncd" % (snapshot_path, name, s), reg) for name, reg in regions.items()]
+                downloaded = False
+                for name, reg in files:
+                    written = False
+                    if snapshot_where == "device":
+                        written = self._snapshot_device(name, info, PFT_SNAP_ASYNC if snapshot_async else 0, reg)
+                        if not written and s != first:
+                            raise RuntimeError("run_series: no state is resident on the device after the solve "
+                                               "(the host-staged path keeps none)")
+                    if not written:
+                        # the host path; with "device" the first snapshot of a host IC, not yet resident
+                        if not downloaded:
+                            drc = self.lib.pft_solver_download(C.byref(self.system))
+                            if drc and not (drc == -2 and s == first):   # -2 at the first: a host IC, nothing resident yet
+                                raise RuntimeError(f"pft_solver_download failed ({drc})")
+                            downloaded = True
+                        save_snapshot(self, name, info, region=reg)
             rows.append(row)
             if rc == 1:
                 break
@@ -836,12 +970,26 @@ def snapshot_info(t, tau, final_time, delta, calc_mode, snapshot=0, total_snapsh
     return info
 
 
-def save_snapshot(sim, path, info):
+def save_snapshot(sim, path, info, region=None, version=0):
     """Write this slab's part of a NetCDF-classic snapshot (pft_io.h); the host array must hold the
-    state (Simulation.download() after a device-resident solve).  Multi-rank: every rank calls it."""
-    rc = lib().pft_snapshot_write(os.fsencode(path), C.byref(sim.grid), _dp(sim.params), C.byref(info), _dp(sim.x))
+    state (Simulation.download() after a device-resident solve).  Multi-rank: every rank calls it.
+    region=sel (f11; see region()): the region dataset of the selected cells instead, byte for byte
+    what Simulation.snapshot_device(region=sel) writes from the resident state; version (1: CDF-1,
+    2: CDF-2, 0: automatic) is taken with a region only."""
+    if region is None:
+        if version:
+            raise ValueError("save_snapshot: version= is taken with region= only")
+        rc = lib().pft_snapshot_write(os.fsencode(path), C.byref(sim.grid), _dp(sim.params), C.byref(info), _dp(sim.x))
+        if rc:
+            raise OSError(f"pft_snapshot_write({path}) failed ({rc})")
+        return
+    if version not in (0, 1, 2):
+        raise ValueError(f"version must be 0, 1 or 2, not {version!r}")
+    r = sim._region(region)
+    rc = lib().pft_snapshot_write_region(os.fsencode(path), C.byref(sim.grid), C.byref(r), _dp(sim.params),
+                                         C.byref(info), _dp(sim.x), version)
     if rc:
-        raise OSError(f"pft_snapshot_write({path}) failed ({rc})")
+        raise OSError(f"pft_snapshot_write_region({path}) failed ({rc})")
 
 
 def read_snapshot_info(path):

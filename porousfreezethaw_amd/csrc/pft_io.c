@@ -80,6 +80,11 @@ static int put_att_int(buf_t * b, const char * name, int v)
 {
 	return put_name(b, name) || put32(b, NCT_INT) || put32(b, 1) || put32(b, (uint32_t)v);
 }
+static int put_att_int3(buf_t * b, const char * name, const int * v)
+{
+	return put_name(b, name) || put32(b, NCT_INT) || put32(b, 3) || put32(b, (uint32_t)v[0]) ||
+	       put32(b, (uint32_t)v[1]) || put32(b, (uint32_t)v[2]);
+}
 static int put_att_text(buf_t * b, const char * name, const char * s)
 {
 	size_t n = strlen(s), pad = (4 - n % 4) % 4;
@@ -95,6 +100,7 @@ typedef struct {
 	uint64_t begin[6];     /* n3, n2, n1, u, p, gl */
 	uint64_t vsize[6];
 	uint64_t total;
+	const pft_region * reg; /* f11: the dataset of a region (NULL: the whole grid's) */
 } layout_t;
 
 static int build_header(buf_t * b, layout_t * L, const pft_grid * g, const double * param,
@@ -112,7 +118,7 @@ static int build_header(buf_t * b, layout_t * L, const pft_grid * g, const doubl
 	rc |= put_name(b, "n2") || put32(b, (uint32_t)L->n2);
 	rc |= put_name(b, "n1") || put32(b, (uint32_t)L->n1);
 	/* global attributes (:2382-2406) */
-	rc |= put32(b, NC_ATTRIBUTE) || put32(b, (uint32_t)(3 + NPARAM + 8));
+	rc |= put32(b, NC_ATTRIBUTE) || put32(b, (uint32_t)(3 + NPARAM + 8 + (L->reg ? 3 : 0)));
 	rc |= put_att_double(b, "L1", g->L1) || put_att_double(b, "L2", g->L2) || put_att_double(b, "L3", g->L3);
 	for(q = 0; q < NPARAM; q++) rc |= put_att_double(b, param_order[q].name, param[param_order[q].idx]);
 	rc |= put_att_int(b, "calc_mode", info->calc_mode);
@@ -120,6 +126,9 @@ static int build_header(buf_t * b, layout_t * L, const pft_grid * g, const doubl
 	rc |= put_att_double(b, "t", info->t) || put_att_double(b, "final_time", info->final_time);
 	rc |= put_att_int(b, "snapshot", info->snapshot) || put_att_int(b, "total_snapshots", info->total_snapshots);
 	rc |= put_att_text(b, "title", info->title);
+	if(L->reg)
+		rc |= put_att_int3(b, "region_start", L->reg->start) || put_att_int3(b, "region_count", L->reg->count) ||
+		      put_att_int3(b, "region_stride", L->reg->stride);
 	/* variables (:2350-2354) */
 	rc |= put32(b, NC_VARIABLE) || put32(b, 6);
 	for(q = 0; q < 6; q++) {
@@ -140,6 +149,7 @@ static int make_layout(buf_t * b, layout_t * L, const pft_grid * g, const double
 {
 	int q;
 	L->n1 = g->n1; L->n2 = g->n2; L->n3 = g->total_n3;
+	if(L->reg) { L->n1 = L->reg->count[0]; L->n2 = L->reg->count[1]; L->n3 = L->reg->count[2]; }
 	L->vsize[0] = 8 * (uint64_t)L->n3; L->vsize[1] = 8 * (uint64_t)L->n2; L->vsize[2] = 8 * (uint64_t)L->n1;
 	for(q = 3; q < 6; q++) L->vsize[q] = 8 * (uint64_t)L->n1 * L->n2 * L->n3;
 	L->version = version ? version : 1;
@@ -189,8 +199,9 @@ static int read_all(int fd, void * p, size_t n, off_t off)
 	return 0;
 }
 
-int pft_snapshot_create(const char * path, const pft_grid * g, const double * param,
-                        const pft_snapshot_info * info, int version)
+/* the header and the coordinate variables of the grid's dataset (reg NULL) or of a region's */
+static int create_dataset(const char * path, const pft_grid * g, const pft_region * reg, const double * param,
+                          const pft_snapshot_info * info, int version)
 {
 	buf_t b = {0};
 	layout_t L;
@@ -199,6 +210,7 @@ int pft_snapshot_create(const char * path, const pft_grid * g, const double * pa
 	uint64_t * coord;
 	if(!path || !g || !param || !info || version < 0 || version > 2) return -2;
 	if(g->n1 < 1 || g->n2 < 1 || g->total_n3 < 1) return -2;
+	L.reg = reg;
 	if((rc = make_layout(&b, &L, g, param, info, version))) { free(b.p); return rc; }
 	fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);           /* NC_CLOBBER */
 	if(fd < 0) { free(b.p); return -1; }
@@ -210,7 +222,12 @@ int pft_snapshot_create(const char * path, const pft_grid * g, const double * pa
 		const long n = q == 0 ? L.n3 : q == 1 ? L.n2 : L.n1;
 		const double Ld = q == 0 ? g->L3 : q == 1 ? g->L2 : g->L1;
 		const double nd = (double)(q == 0 ? g->total_n3 : q == 1 ? g->n2 : g->n1);
-		for(k = 0; k < n; k++) coord[k] = d2be(Ld * (0.5 + k - 0) / nd);
+		if(!reg) for(k = 0; k < n; k++) coord[k] = d2be(Ld * (0.5 + k - 0) / nd);
+		else for(k = 0; k < n; k++) {
+			/* the same expression at the selected index: the full dataset's entry, bit for bit */
+			const long kk = reg->start[2 - q] + k * (long)reg->stride[2 - q];
+			coord[k] = d2be(Ld * (0.5 + kk - 0) / nd);
+		}
 		rc = write_all(fd, coord, 8 * (size_t)n, (off_t)L.begin[q]);
 	}
 	free(coord);
@@ -218,6 +235,19 @@ int pft_snapshot_create(const char * path, const pft_grid * g, const double * pa
 	if(close(fd) && !rc) rc = -1;
 	free(b.p);
 	return rc;
+}
+
+int pft_snapshot_create(const char * path, const pft_grid * g, const double * param,
+                        const pft_snapshot_info * info, int version)
+{
+	return create_dataset(path, g, NULL, param, info, version);
+}
+
+int pft_snapshot_create_region(const char * path, const pft_grid * g, const pft_region * r, const double * param,
+                               const pft_snapshot_info * info, int version)
+{
+	if(!g || !r || pft_region_check(g, r)) return -2;
+	return create_dataset(path, g, r, param, info, version);
 }
 
 /* begin offsets of u, p, gl from a dataset's header (shared by read and write_slab) */
@@ -490,9 +520,88 @@ int pft_snapshot_slab_ranges(const char * path, const pft_grid * g, pft_snapshot
 	return 0;
 }
 
+/* ---------------------------------------------------------------------------------------- */
+/* f11: regions */
+
+int pft_region_check(const pft_grid * g, const pft_region * r)
+{
+	int a;
+	if(!g || !r) return -2;
+	for(a = 0; a < 3; a++) {
+		const long n = a == 0 ? g->n1 : a == 1 ? g->n2 : g->total_n3;
+		if(r->start[a] < 0 || r->count[a] < 1 || r->stride[a] < 1) return -2;
+		if(r->start[a] + (r->count[a] - 1) * (long)r->stride[a] >= n) return -2;
+	}
+	return 0;
+}
+
+int pft_region_local(const pft_grid * g, const pft_region * r, int * kfirst, int * kcount, int * klocal)
+{
+	long lo, hi, m0, m1;
+	const long s = r ? r->stride[2] : 1;
+	if(!g || !r || !kfirst || !kcount || !klocal || pft_region_check(g, r)) return -2;
+	lo = g->first_row; hi = lo + g->n3;                             /* the slab's global planes [lo, hi) */
+	/* the first m with start + m*stride >= lo: the stride's phase is kept across the slab boundary
+	   (rounded up from start, not from 0) */
+	m0 = lo <= r->start[2] ? 0 : (lo - r->start[2] + s - 1) / s;
+	/* the last m with start + m*stride < hi */
+	m1 = hi - 1 < r->start[2] ? -1 : (hi - 1 - r->start[2]) / s;
+	if(m1 > r->count[2] - 1) m1 = r->count[2] - 1;
+	if(m0 > r->count[2]) m0 = r->count[2];
+	*kfirst = (int)m0;
+	*kcount = m1 >= m0 ? (int)(m1 - m0 + 1) : 0;
+	*klocal = *kcount ? (int)(r->start[2] + m0 * s - lo) : 0;
+	return 0;
+}
+
+size_t pft_region_image_bytes(const pft_grid * g, const pft_region * r)
+{
+	int kfirst, kcount, klocal;
+	if(pft_region_local(g, r, &kfirst, &kcount, &klocal)) return 0;
+	return 3 * 8 * (size_t)kcount * (size_t)r->count[1] * (size_t)r->count[0];
+}
+
+int pft_region_image_host(const pft_grid * g, const pft_region * r, const double * x, void * out)
+{
+	int kfirst, kcount, klocal;
+	long q, k, j, i;
+	uint64_t * o = (uint64_t *)out;
+	if(!x || !out || pft_region_local(g, r, &kfirst, &kcount, &klocal)) return -2;
+	{
+		const long N1 = g->n1 + 2 * PFT_BCOND_THICKNESS, N2 = g->n2 + 2 * PFT_BCOND_THICKNESS;
+		const long N3 = g->n3 + 2 * PFT_BCOND_THICKNESS, S = N1 * N2 * N3;
+		for(q = 0; q < 3; q++)
+			for(k = 0; k < kcount; k++)
+				for(j = 0; j < r->count[1]; j++) {
+					const long kk = klocal + k * r->stride[2], jj = r->start[1] + j * r->stride[1];
+					const double * row = x + q * S + ((kk + PFT_BCOND_THICKNESS) * N2 + jj + PFT_BCOND_THICKNESS) * N1 +
+					                     PFT_BCOND_THICKNESS + r->start[0];
+					for(i = 0; i < r->count[0]; i++) *o++ = d2be(row[i * r->stride[0]]);
+				}
+	}
+	return 0;
+}
+
+int pft_snapshot_region_ranges(const char * path, const pft_grid * g, const pft_region * r, pft_snapshot_ranges * ranges)
+{
+	parsed_t P;
+	int fd, rc, q, kfirst, kcount, klocal;
+	if(!path || !ranges || pft_region_local(g, r, &kfirst, &kcount, &klocal)) return -2;
+	if((fd = open(path, O_RDONLY)) < 0) return -1;
+	rc = parse_header(fd, &P);
+	close(fd);
+	if(rc) return rc;
+	if(P.n1 != r->count[0] || P.n2 != r->count[1] || P.n3 != r->count[2]) return -4;
+	ranges->bytes = 8ULL * (uint64_t)kcount * (uint64_t)r->count[1] * (uint64_t)r->count[0];
+	for(q = 0; q < 3; q++)
+		ranges->off[q] = P.begin[q] + 8ULL * (uint64_t)kfirst * (uint64_t)r->count[1] * (uint64_t)r->count[0];
+	return 0;
+}
+
 static int image_io(const char * path, const pft_snapshot_ranges * r, void * image, int writing)
 {
 	int fd, rc = 0, q, e;
+	if(r->bytes == 0) return 0;                                     /* a slab that owns none of a region */
 	if((fd = open(path, writing ? O_WRONLY : O_RDONLY)) < 0) return -1;
 	for(q = 0; q < 3 && !rc; q++) {
 		char * at = (char *)image + (size_t)q * r->bytes;
@@ -505,14 +614,39 @@ static int image_io(const char * path, const pft_snapshot_ranges * r, void * ima
 
 int pft_snapshot_write_image(const char * path, const pft_snapshot_ranges * r, const void * image)
 {
-	if(!path || !r || !image) return -2;
+	if(!path || !r || (!image && r->bytes)) return -2;
 	return image_io(path, r, (void *)image, 1);
 }
 
 int pft_snapshot_read_image(const char * path, const pft_snapshot_ranges * r, void * image)
 {
-	if(!path || !r || !image) return -2;
+	if(!path || !r || (!image && r->bytes)) return -2;
 	return image_io(path, r, image, 0);
+}
+
+int pft_snapshot_write_region(const char * path, const pft_grid * g, const pft_region * r, const double * param,
+                              const pft_snapshot_info * info, const double * x, int version)
+{
+	pft_comm * c = pft_comm_current();
+	pft_snapshot_ranges ranges;
+	long long err = 0;
+	void * image = NULL;
+	int rc = 0;
+	if(!g || !r || !x || pft_region_check(g, r)) return -2;          /* the same on every rank */
+	if(g->rank == 0) rc = pft_snapshot_create_region(path, g, r, param, info, version);
+	err = rc ? 1 : 0;
+	pft_comm_allreduce_max_i64(c, &err);                           /* also the barrier */
+	if(err) return rc ? rc : -1;
+	rc = pft_snapshot_region_ranges(path, g, r, &ranges);
+	if(!rc && ranges.bytes) {
+		if(!(image = malloc(3 * (size_t)ranges.bytes))) rc = -1;
+		if(!rc) rc = pft_region_image_host(g, r, x, image);
+		if(!rc) rc = pft_snapshot_write_image(path, &ranges, image);
+		free(image);
+	}
+	err = rc ? 1 : 0;
+	pft_comm_allreduce_max_i64(c, &err);
+	return rc ? rc : (err ? -1 : 0);
 }
 
 /* One writer thread per process, started by the first job.  Jobs are written in the order they
@@ -564,7 +698,8 @@ static void * writer_main(void * arg)
 int pft_snapshot_write_image_async(const char * path, const pft_snapshot_ranges * r, const void * image)
 {
 	snap_job * j;
-	if(!path || !r || !image) return -2;
+	if(!path || !r || (!image && r->bytes)) return -2;
+	if(r->bytes == 0) return 0;                                     /* nothing to write: no job */
 	if(!(j = (snap_job *)calloc(1, sizeof *j))) return -1;
 	if(!(j->path = strdup(path))) { free(j); return -1; }
 	j->r = *r;

@@ -2466,6 +2466,8 @@ int pft_slab_create(pft_slab** out, const pft_slab_desc* d, const pft_consts* c)
     s->timeout_s = (et && atof(et) > 0.0) ? atof(et) : 300.0;
     const char* edg = getenv("PFT_DIAG_WGS");
     s->diag_wgs = (edg && atoi(edg) > 0) ? atoi(edg) : 0;
+    const char* erg = getenv("PFT_REGION_WGS");
+    s->region_wgs = (erg && atoi(erg) > 0) ? atoi(erg) : 0;
   }
   const size_t bytes = sizeof(double) * (3 * (size_t)s->fs + 2 * (size_t)s->plane);
   hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);

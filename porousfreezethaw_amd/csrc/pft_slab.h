@@ -5,7 +5,7 @@
 //   pft_kernels.hip  the step kernels (merson_stage, merson_fused, merson_pair), the slab object's
 //                    API, the pft_hip_* shim, the halo exchange, IC
 //   pft_reduce.hip   diagnostics and exact means (f5, f6)
-//   pft_snap.hip     snapshots (f7)
+//   pft_snap.hip     snapshots (f7), region snapshots (f11)
 // No device code crosses files: nothing is device-linked.  Every .hip includes this header first.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -208,6 +208,7 @@ struct pft_slab {
   void* snap_stage;
   int snap_timing;
   hipEvent_t ev_snap[2];
+  int region_wgs;        // f11: cap on region_kernel's workgroups; 0: 8 per CU (env PFT_REGION_WGS: tests)
   double timeout_s;    // bound on a host wait for the compute stream while ipc peers are on
                          // (env PFT_IPC_TIMEOUT, default 300 s; slab_wait)
   pft_slab_watch_fn watch;   // communicator watchdog (RCCL: async error / expiry -> abort)

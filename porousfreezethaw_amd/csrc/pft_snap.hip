@@ -1,4 +1,5 @@
-// pft_snap.hip -- device-side snapshots: snap_kernel, export, import and the pinned image.
+// pft_snap.hip -- device-side snapshots: snap_kernel, export, import and the pinned image (f7);
+// region_kernel and the region image (f11).
 #include "pft_slab.h"
 
 #pragma clang fp contract(off)
@@ -162,6 +163,98 @@ static int snap_export_enqueue(pft_slab* s, int buf, void* dst)
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// f11: the region image (pft_io.h) -- the cells start + m*stride of a box, per field a dense
+// [c3][c2][c1] block of big-endian words.  One flat kernel, blockIdx.y the field: a lane moves one
+// word per trip of a grid-stride loop -- an 8-byte load from the strided box, the integer byte swap
+// of snap_kernel, an 8-byte store at the flat output index -- so the stores are dense and coalesced
+// for every region and the loads are coalesced when stride[0] == 1.  No LDS, no atomic; only
+// interior planes are addressed (plane 1 + klocal + k'*s3 of the buffer's indexing).
+// The split of the flat index into (k', j', i'): a lane divides once, before the loop.  Every trip
+// advances all lanes by the same number of words, gridDim.x * PFT_SNAP_BLOCK, whose own split
+// (dk, dj, di) is wave-uniform and computed once; the lane adds it digit by digit with one carry
+// each (i' + di < 2 c1, j' + dj + 1 <= 2 c2 - 1), so the loop holds no division whatever the row
+// length -- a row of one word (a y-z section) walks as cheaply as a row of 200.
+
+struct RegionGeom {
+  long plane, n1;             // words per plane and per row of the slab
+  long n;                     // words per field of the image: c1 * c2 * c3
+  int i0, j0, k0;             // first selected cell; k0 slab-local (interior plane, 0-based)
+  int s1, s2, s3;
+  int c1, c2;
+};
+
+__global__ __launch_bounds__(PFT_SNAP_BLOCK) void region_kernel(const snap_u64* __restrict__ src, long src_stride,
+                                                                snap_u64* __restrict__ dst, RegionGeom g)
+{
+  const snap_u64* sp = src + (long)blockIdx.y * src_stride;   // plane 0 of the field: the ghost plane
+  snap_u64* dp = dst + (long)blockIdx.y * g.n;
+  const long step = (long)gridDim.x * PFT_SNAP_BLOCK;
+  const long row = g.c1, slice = (long)g.c1 * g.c2;
+  // the step's split: uniform
+  const long dk = step / slice, srem = step - dk * slice;
+  const int dj = (int)(srem / row), di = (int)(srem - (long)dj * row);
+  // the lane's split: once
+  long o = (long)blockIdx.x * PFT_SNAP_BLOCK + threadIdx.x;
+  long k = o / slice;
+  const long orem = o - k * slice;
+  int j = (int)(orem / row), i = (int)(orem - (long)j * row);
+  for (; o < g.n; o += step) {
+    const long at = g.plane * (1 + g.k0 + k * g.s3) + (long)(g.j0 + j * g.s2) * g.n1 + g.i0 + (long)i * g.s1;
+    dp[o] = __builtin_bswap64(sp[at]);
+    i += di;
+    const int ci = i >= g.c1;
+    i -= ci ? g.c1 : 0;
+    j += dj + ci;
+    const int cj = j >= g.c2;
+    j -= cj ? g.c2 : 0;
+    k += dk + cj;
+  }
+}
+
+// 0: r is a region of the slab's interior (count[2] == 0 allowed: nothing to move)
+static int region_local_ok(const pft_slab* s, const pft_region* r)
+{
+  const int n[3] = {s->d.n1, s->d.n2, s->d.n3};
+  for (int a = 0; a < 3; ++a) {
+    if (r->start[a] < 0 || r->stride[a] < 1 || r->count[a] < (a == 2 ? 0 : 1)) return -2;
+    if (r->count[a] > 0 && r->start[a] + (long)(r->count[a] - 1) * r->stride[a] >= n[a]) return -2;
+  }
+  return 0;
+}
+
+static bool region_is_interior(const pft_slab* s, const pft_region* r)
+{
+  return r->start[0] == 0 && r->start[1] == 0 && r->start[2] == 0 && r->stride[0] == 1 && r->stride[1] == 1 &&
+         r->stride[2] == 1 && r->count[0] == s->d.n1 && r->count[1] == s->d.n2 && r->count[2] == s->d.n3;
+}
+
+// the region kernel of buffer `buf` into dst, enqueued on the compute stream (no wait); the slab's
+// whole interior at stride 1 is the f7 image: that export, with its 16-byte accesses
+static int region_export_enqueue(pft_slab* s, int buf, const pft_region* r, void* dst)
+{
+  if (region_is_interior(s, r)) return snap_export_enqueue(s, buf, dst);
+  RegionGeom g;
+  g.plane = s->plane;
+  g.n1 = s->d.n1;
+  g.n = (long)r->count[0] * r->count[1] * r->count[2];
+  g.i0 = r->start[0], g.j0 = r->start[1], g.k0 = r->start[2];
+  g.s1 = r->stride[0], g.s2 = r->stride[1], g.s3 = r->stride[2];
+  g.c1 = r->count[0], g.c2 = r->count[1];
+  // all resident at once, as snap_blocks; PFT_REGION_WGS caps it further (tests: several trips)
+  const long cap = s->region_wgs > 0 ? s->region_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
+  long wgs = (g.n + PFT_SNAP_BLOCK - 1) / PFT_SNAP_BLOCK;
+  if (wgs > cap) wgs = cap;
+  if (s->snap_timing) HIPCHK(hipEventRecord(s->ev_snap[0], s->stream));
+  if (g.n > 0) {
+    region_kernel<<<dim3((unsigned)wgs, 3), PFT_SNAP_BLOCK, 0, s->stream>>>(reinterpret_cast<const snap_u64*>(s->buf[buf]), s->fs,
+                                                                           (snap_u64*)dst, g);
+    HIPCHK(hipGetLastError());
+  }
+  if (s->snap_timing) HIPCHK(hipEventRecord(s->ev_snap[1], s->stream));
+  return 0;
+}
+
 static int snap_ensure_host(pft_slab* s)
 {
   if (s->snap_host) return 0;
@@ -241,6 +334,41 @@ int pft_slab_snapshot_export(pft_slab* s, int buf, int link, void** image)
     HIPCHK(hipMemcpyAsync(s->snap_host, s->snap_stage, bytes, hipMemcpyDeviceToHost, s->stream));
   }
   if ((rc = slab_wait(s, nullptr, "pft_slab_snapshot_export"))) return rc;
+  *image = s->snap_host;
+  return 0;
+}
+
+size_t pft_slab_region_image_bytes(const pft_region* r)
+{
+  return r ? 3 * sizeof(double) * (size_t)r->count[0] * (size_t)r->count[1] * (size_t)r->count[2] : 0;
+}
+
+int pft_slab_export_region_be(pft_slab* s, int buf, const pft_region* r, void* dst)
+{
+  if (!s || !r || !dst || buf < 0 || buf >= PFT_BUF_COUNT || ((uintptr_t)dst & 7) || region_local_ok(s, r)) return -2;
+  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_export_region_be");
+  const int rc = region_export_enqueue(s, buf, r, dst);
+  if (rc) return rc;
+  return slab_wait(s, nullptr, "pft_slab_export_region_be");
+}
+
+int pft_slab_region_export(pft_slab* s, int buf, const pft_region* r, int link, void** image)
+{
+  if (!s || !r || !image || buf < 0 || buf >= PFT_BUF_COUNT || link < 0 || link > 1 || region_local_ok(s, r)) return -2;
+  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_region_export");
+  int rc = snap_ensure_host(s);
+  if (rc) return rc;
+  // a job of the background writer may still read the buffer's previous image
+  (void)pft_snapshot_writer_release(s->snap_host);
+  const size_t bytes = pft_slab_region_image_bytes(r);   // at most the full image's: the box lies in the interior
+  if (link == PFT_SNAP_LINK_DIRECT) {
+    if ((rc = region_export_enqueue(s, buf, r, s->snap_host_dev))) return rc;
+  } else {
+    if (!s->snap_stage) HIPCHK(hipMalloc(&s->snap_stage, pft_slab_image_bytes(s)));
+    if ((rc = region_export_enqueue(s, buf, r, s->snap_stage))) return rc;
+    if (bytes) HIPCHK(hipMemcpyAsync(s->snap_host, s->snap_stage, bytes, hipMemcpyDeviceToHost, s->stream));
+  }
+  if ((rc = slab_wait(s, nullptr, "pft_slab_region_export"))) return rc;
   *image = s->snap_host;
   return 0;
 }

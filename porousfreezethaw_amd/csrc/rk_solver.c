@@ -976,6 +976,71 @@ int pft_solver_snapshot_write(const char * path, const double * param, const pft
 	return snap_agree(rc);
 }
 
+/* f11: the region with its k triple made slab-local (what the slab's entries take) */
+static int region_of_slab(const pft_region * region, pft_region * loc, int * kfirst)
+{
+	int kcount, klocal, rc;
+	if((rc = pft_region_local(&R.slab_grid, region, kfirst, &kcount, &klocal))) return rc;
+	*loc = *region;
+	loc->start[2] = klocal;
+	loc->count[2] = kcount;
+	return 0;
+}
+
+int pft_solver_snapshot_region_write(const char * path, const double * param, const pft_snapshot_info * info,
+                                     const pft_region * region, int flags)
+{
+	pft_comm * c = comm();
+	const int nprocs = pft_comm_size(c), version = (flags >> 8) & 3;
+	pft_snapshot_ranges r;
+	pft_region loc;
+	void * image = NULL;
+	int rc = 0, kfirst;
+	if(!path || !param || !info || !region || version > 2) return -2;
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if(R.in_callback && nprocs > 1) return -2;
+	/* the region is judged against the whole grid, which every rank holds: the same answer everywhere */
+	if(pft_region_check(&R.slab_grid, region)) return -2;
+	if(R.slab_grid.rank == 0) rc = pft_snapshot_create_region(path, &R.slab_grid, region, param, info, version);
+	if((rc = snap_agree(rc))) return rc;
+	rc = pft_snapshot_region_ranges(path, &R.slab_grid, region, &r);
+	if(!rc) rc = region_of_slab(region, &loc, &kfirst);
+	if(!rc && loc.count[2] > 0) {
+		if((rc = pft_slab_region_export(R.slab, PFT_BUF_X, &loc, snap_link(flags), &image))) {
+			R.last_status = rc;
+			rc = PFT_SOLVE_DEVICE_ERROR;
+		}
+		if(!rc) rc = pft_snapshot_write_image_async(path, &r, image);
+	}
+	if(!rc && !(flags & PFT_SNAP_ASYNC)) rc = pft_snapshot_writer_wait();
+	return snap_agree(rc);
+}
+
+int pft_solver_region(const pft_region * region, double * out_native)
+{
+	pft_region loc;
+	void * image = NULL;
+	int rc, kfirst;
+	size_t n, w;
+	if(!region) return -2;
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if((rc = region_of_slab(region, &loc, &kfirst))) return rc;
+	n = 3 * (size_t)loc.count[0] * (size_t)loc.count[1] * (size_t)loc.count[2];
+	if(n == 0) return 0;
+	if(!out_native) return -2;
+	if((rc = pft_slab_region_export(R.slab, PFT_BUF_X, &loc, snap_link(0), &image))) {
+		R.last_status = rc;
+		return PFT_SOLVE_DEVICE_ERROR;
+	}
+	for(w = 0; w < n; w++) {
+		unsigned long long v;
+		memcpy(&v, (const char *)image + 8 * w, 8);
+		v = __builtin_bswap64(v);
+		memcpy(out_native + w, &v, 8);
+	}
+	return 0;
+}
+
 int pft_solver_snapshot_wait(void)
 {
 	return snap_agree(pft_snapshot_writer_wait());

@@ -513,7 +513,8 @@ class Case:
         return snap, total, t, final, tau
 
     def run(self, nprocs=1, rank=0, beads=None, snapshot_path=None, comment="", diag=True, opts=None,
-            means=False, snapshot_where="host", snapshot_async=False, **kw):
+            means=False, snapshot_where="host", snapshot_async=False, regions=None, region_every=1,
+            snapshot_full=True, **kw):
         """the whole case as the driver runs it (intertrack.c:2265-2283): this slab's simulation
         (simulation(); **kw goes to it), then saved_files snapshots up to final_time
         (Simulation.run_series; means=True: every row also carries the exact means).  Returns the
@@ -522,7 +523,11 @@ class Case:
         background).  With `set icond_file` the state is read from that dataset; with `set
         continue_series` as well, the series goes on from it (intertrack.c:1642-1669): the starting
         snapshot, total_snapshots, t, final_time and tau come from its attributes, rows and files
-        are numbered from the starting snapshot, which is written again unless `set skip_icond`."""
+        are numbered from the starting snapshot, which is written again unless `set skip_icond`.
+        regions / region_every / snapshot_full: run_series' region datasets (f11), given here in
+        Python.  The parameter file's slice_output, slice_along and slice_reverse_order stay the
+        no-ops they are in the reference driver, which parses and skips them (they belong to its
+        slicing tool): no Params word selects a region."""
         final_time, saved_files, first, skip_first = self.final_time, self.saved_files, 0, False
         if self.continue_series and not self.icond_mode:
             warnings.warn("continue_series is only meaningful when the initial conditions are loaded from file")
@@ -534,7 +539,8 @@ class Case:
         try:
             return sim.run_series(final_time, saved_files, snapshot_path=snapshot_path, comment=comment,
                                   diag=diag, opts=opts, means=means, snapshot_where=snapshot_where,
-                                  snapshot_async=snapshot_async, first_snapshot=first, skip_first=skip_first)
+                                  snapshot_async=snapshot_async, first_snapshot=first, skip_first=skip_first,
+                                  regions=regions, region_every=region_every, snapshot_full=snapshot_full)
         finally:
             sim.close()
 
