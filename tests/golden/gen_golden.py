@@ -39,6 +39,9 @@ Cases (SURVEY.md section 4.2 KATs 1-4):
            case's grid from its IC to t = 36 s: DELTA_LOCAL (hybrid2.c:578), per-variable
            chunk_eps_mult (0.25, 3, 7) (hybrid2.c:521), both, and multipliers that vary inside a
            variable (x1 on even planes, x2.5 on odd ones); each checked identical on 3 ranks.
+  gthaw    g20 with phase_switch_time 100 s: the trajectory record for calc_mode 0, 1 and 2 to
+           t = 36, 360 and 720 s across the freeze-to-thaw switch of the top temperature
+           (equation.c:96-111), checked identical on 3 ranks.
 
     python tests/golden/gen_golden.py [case ...]     (default: all)
 """
@@ -210,6 +213,50 @@ def case_g20nf():
                 arrays[f"traj_m{mode}_state{i}"] = x
             meta[f"traj_m{mode}"] = tm
             meta[f"m{mode}_params"] = hexify(p)
+        finally:
+            wm.close()
+    return arrays, meta
+
+
+GTHAW_SWITCH = 100.0
+
+
+def case_gthaw():
+    """g20 with phase_switch_time 100 s (every published Params has 5 h, past the end of every other
+    golden): the Dirichlet temperature on the top planes jumps from top_temp1 to top_temp2
+    (equation.c:96-111,175-183) between the first and the second snapshot time, so the record holds
+    the attempted steps that straddle the switch, the rejections the 45 K jump causes and the thaw
+    after it.  Recorded as g20's traj_m*: calc_mode 0, 1 and 2 (mode 2 with p IC = 0) to
+    t = 36, 360 and 720 s, checked identical on 3 ranks."""
+    arrays, meta = {}, {"case": "gthaw", "phase_switch_time": GTHAW_SWITCH,
+                        "source": f"reference Params, grid_nodes 20, phase_switch_time {GTHAW_SWITCH:g}"}
+    times = [36.0, 360.0, 720.0]
+    meta["traj_times"] = times
+    for mode, rep in ((0, {}), (1, {}), (2, {"icond p": "0"})):
+        r = {"grid_nodes": 20, "calc_mode": mode, "phase_switch_time": repr(GTHAW_SWITCH)}
+        r.update(rep)
+        wm = Work(r)
+        try:
+            o = wm.run(1, "setup")
+            p = read_params(o)
+            assert p["phase_switch_time"] == GTHAW_SWITCH and p["calc_mode"] == mode
+            shape = (3, p["n3"], p["n2"], p["n1"])
+            if mode == 0:
+                meta["params"] = hexify(p)
+            meta[f"m{mode}_params"] = hexify(p)
+            ic_m = load(os.path.join(o, "ic.f64"), shape)
+            icp = os.path.join(wm.dir, "icm.f64")
+            ic_m.tofile(icp)
+            o1 = wm.run(1, "solve", icp, 0.0, 1.0, *times)
+            tm, st = traj(o1, len(times), shape)
+            o3 = wm.run(3, "solve", icp, 0.0, 1.0, *times)
+            tm3, st3 = traj(o3, len(times), shape)
+            assert tm == tm3 and all(np.array_equal(a, b) for a, b in zip(st, st3)), \
+                f"decomposition invariance broken for mode {mode}"
+            arrays[f"traj_m{mode}_ic"] = ic_m
+            for i, s in enumerate(st):
+                arrays[f"traj_m{mode}_state{i}"] = s
+            meta[f"traj_m{mode}"] = tm
         finally:
             wm.close()
     return arrays, meta
@@ -507,7 +554,7 @@ def main():
     if not os.path.exists(PFT_REF):
         sys.exit("build the reference harness first: make -C oracle ref")
     cases = {"g20": case_g20, "ragged": case_ragged, "g100": case_g100, "ctl": case_ctl, "g200": case_g200,
-             "g400": case_g400, "g20nf": case_g20nf, "gnoise": case_gnoise, "epsctl": case_epsctl}
+             "g400": case_g400, "g20nf": case_g20nf, "gnoise": case_gnoise, "epsctl": case_epsctl, "gthaw": case_gthaw}
     for name in sys.argv[1:] or list(cases):
         arrays, meta = cases[name]()
         name = meta["case"]

@@ -101,6 +101,36 @@ def test_bcond_setup_host_bitwise(tag):
         sim.close()
 
 
+def test_host_model_top_temperature_at_the_phase_switch():
+    """the host model's choice of the Dirichlet top temperature (bcond_setup, equation.c:96-111:
+    top_temp1 while t < phase_switch_time, top_temp2 from it on) at the last double before the
+    switch, at the switch and at the first double after it, on tests/golden/gthaw (switch at 100 s).
+    libpft's host side of the right-hand side is this ghost fill (f_generic_model01 runs it on the
+    caller's array, then the device stencil); here the oracle's stencil stands in for the device,
+    so host fill + stencil must equal the oracle's own RHS, and the ghost cells its own"""
+    meta, A = O.load_case("gthaw")
+    Pm, info = O.params_from_meta(meta)
+    sw = Pm[O.PARAM_NAMES.index("phase_switch_time")]
+    assert sw == 100.0
+    g = O.make_grid(info)
+    K = []
+    for t in (np.nextafter(sw, 0.0), sw, np.nextafter(sw, np.inf)):
+        sim = _sim_from_case(meta, A, "traj_m0_ic", mode=0)
+        P.lib().bcond_setup(float(t), P._dp(sim.x))
+        w = np.ascontiguousarray(sim.padded())
+        dw = np.zeros_like(w)
+        O.lib().pft_or_stencil(C.byref(g), O.ptr(Pm), 0, O.ptr(w), None, O.ptr(dw))
+        sim.close()
+        Ko, ws = O.rhs(info, Pm, 0, float(t), A["traj_m0_ic"])
+        assert np.array_equal(w, ws[0]), t
+        assert np.array_equal(O.unpad(g, dw), Ko), t
+        top = w[0, -2:]
+        assert np.all(top == Pm[O.PARAM_NAMES.index("top_temp1" if t < sw else "top_temp2")]), t
+        K.append(Ko)
+    assert not np.array_equal(K[0], K[1])
+    assert np.array_equal(K[1], K[2])
+
+
 def test_initial_condition_bitwise():
     """pft_model_ic_default + PrecalculateData glass beads vs the reference's IC (Params:9-21
     through its expression evaluator, equation.c:459-530)"""

@@ -9,6 +9,7 @@ import pytest
 
 import _oracle as O
 import porousfreezethaw_amd as P
+from _loopback import run_slabs
 
 pytestmark = pytest.mark.gpu
 
@@ -175,41 +176,20 @@ def test_matches_oracle_larger_grid(dims, flavour):
 
 
 def _loopback_run(meta, initial, nprocs, times, mode=0, gl_static=False, flavour="fused32"):
-    L = P.lib()
-    group = C.c_void_p()
-    assert L.pft_comm_init_loopback(C.byref(group), nprocs) == 0
-    out, errs = [None] * nprocs, []
+    def body(r):
+        Pm, info = O.params_from_meta(meta)
+        sim = P.Simulation(info["n1"], info["n2"], info["n3"], (info["L1"], info["L2"], info["L3"]), mode,
+                           Pm, nprocs=nprocs, rank=r, initial=initial, tau=1.0, tau_min=info["tau_min"],
+                           delta=info["delta"], gl_static=gl_static, tile=FLAVOURS[flavour][0],
+                           recompute=FLAVOURS[flavour][1])
+        res = []
+        for T in times:
+            rc = sim.solve(T)
+            res.append((sim.t, sim.h, sim.system.steps, sim.system.steps_total, rc, sim.interior()))
+        sim.close()
+        return res
 
-    def worker(r):
-        try:
-            mine = C.c_void_p()
-            assert L.pft_comm_loopback_rank(group, r, C.byref(mine)) == 0
-            L.pft_comm_set_current(mine)
-            Pm, info = O.params_from_meta(meta)
-            sim = P.Simulation(info["n1"], info["n2"], info["n3"], (info["L1"], info["L2"], info["L3"]), mode,
-                               Pm, nprocs=nprocs, rank=r, initial=initial, tau=1.0, tau_min=info["tau_min"],
-                               delta=info["delta"], gl_static=gl_static, tile=FLAVOURS[flavour][0],
-                               recompute=FLAVOURS[flavour][1])
-            res = []
-            for T in times:
-                rc = sim.solve(T)
-                res.append((sim.t, sim.h, sim.system.steps, sim.system.steps_total, rc, sim.interior()))
-            out[r] = res
-            sim.close()
-            L.pft_comm_set_current(None)
-            L.pft_comm_destroy(mine)
-        except BaseException as e:   # noqa: BLE001 -- surfaced below
-            errs.append(e)
-
-    ths = [threading.Thread(target=worker, args=(r,)) for r in range(nprocs)]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join(timeout=600)
-    L.pft_comm_destroy(group)
-    if errs:
-        raise errs[0]
-    return out
+    return run_slabs(nprocs, body)
 
 
 @pytest.mark.parametrize("nprocs", [2, 4])

@@ -113,6 +113,31 @@ def test_trajectory_no_flux_modes_bitwise(mode):
         assert np.array_equal(x, A[f"traj_m{mode}_state{i}"])
 
 
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_trajectory_across_the_phase_switch_bitwise(mode):
+    """tests/golden/gthaw: g20 with phase_switch_time = 100 s, so the top temperature jumps from
+    top_temp1 to top_temp2 (equation.c:96-111,175-183) between the first two snapshot times.  The
+    attempted steps that straddle the switch (each stage decides at its own time), the rejections
+    after the 45 K jump and the thaw that follows equal the reference's, and the ice does melt"""
+    meta, A = O.load_case("gthaw")
+    P, info = O.params_from_meta(meta)
+    assert P[O.PARAM_NAMES.index("phase_switch_time")] == meta["phase_switch_time"] == 100.0
+    res = O.solve(info, P, mode, A[f"traj_m{mode}_ic"], 0.0, 1.0, meta["traj_times"])
+    for i, (t, h, s, st, rc, x) in enumerate(res):
+        ref = meta[f"traj_m{mode}"][i]
+        assert (t.hex(), h.hex(), s, st, rc) == (float.fromhex(ref[0]).hex(), float.fromhex(ref[1]).hex(),
+                                                 ref[2], ref[3], ref[4])
+        assert np.array_equal(x, A[f"traj_m{mode}_state{i}"])
+    # the switch is seen: the freeze (tests/golden/g20) has other states from t = 360 s on
+    g20 = O.load_case("g20")[1]
+    assert np.array_equal(A[f"traj_m{mode}_ic"], g20[f"traj_m{mode}_ic"])
+    assert np.array_equal(A[f"traj_m{mode}_state0"], g20[f"traj_m{mode}_state0"])
+    assert not np.array_equal(A[f"traj_m{mode}_state1"], g20[f"traj_m{mode}_state1"])
+    if mode == 0:
+        ice = [int((A[f"traj_m0_state{i}"][1] > 0.5).sum()) for i in range(3)]
+        assert ice[0] > ice[2] > 0, ice
+
+
 # ---- u_noise (tests/golden/gnoise: the reference with u_noise_amp = 0.5 K on one rank) ----------
 
 def test_noise_field_is_glibc_rand_from_seed_1():

@@ -12,6 +12,7 @@ import pytest
 
 import _oracle as O
 import porousfreezethaw_amd as P
+from _loopback import run_slabs
 
 pytestmark = pytest.mark.gpu
 
@@ -211,43 +212,21 @@ def test_pair_full_size_400():
 
 def _loopback_pairs(meta, initial, nprocs, times, dims=None, steps=0, gl_static=False, mode=0):
     """nprocs slabs on one GPU (loopback transport, one host thread each), pair kernels forced"""
-    L = P.lib()
-    group = C.c_void_p()
-    assert L.pft_comm_init_loopback(C.byref(group), nprocs) == 0
-    out, errs = [None] * nprocs, []
+    def body(r):
+        Pm, info = O.params_from_meta(meta)
+        n1, n2, n3 = dims or (info["n1"], info["n2"], info["n3"])
+        sim = P.Simulation(n1, n2, n3, (info["L1"], info["L2"], info["L3"]), mode, Pm, nprocs=nprocs, rank=r,
+                           initial=initial, beads=None if initial is not None else O.beads(), tau=1.0,
+                           tau_min=info["tau_min"], delta=info["delta"], gl_static=gl_static, tile=2)
+        res = []
+        for T in times:
+            rc = sim.solve_ex(T, steps, 0) if steps else sim.solve(T)
+            res.append((sim.t.hex(), sim.h.hex(), sim.system.steps, sim.system.steps_total, rc, sim.interior()))
+        pairs = sim.stats().pairs
+        sim.close()
+        return res, pairs
 
-    def worker(r):
-        try:
-            mine = C.c_void_p()
-            assert L.pft_comm_loopback_rank(group, r, C.byref(mine)) == 0
-            L.pft_comm_set_current(mine)
-            L.pft_solver_set_option(P.PFT_OPT_PAIR, 2)         # per host thread
-            Pm, info = O.params_from_meta(meta)
-            n1, n2, n3 = dims or (info["n1"], info["n2"], info["n3"])
-            sim = P.Simulation(n1, n2, n3, (info["L1"], info["L2"], info["L3"]), mode, Pm, nprocs=nprocs, rank=r,
-                               initial=initial, beads=None if initial is not None else O.beads(), tau=1.0,
-                               tau_min=info["tau_min"], delta=info["delta"], gl_static=gl_static, tile=2)
-            res = []
-            for T in times:
-                rc = sim.solve_ex(T, steps, 0) if steps else sim.solve(T)
-                res.append((sim.t.hex(), sim.h.hex(), sim.system.steps, sim.system.steps_total, rc, sim.interior()))
-            out[r] = (res, sim.stats().pairs)
-            sim.close()
-            L.pft_solver_set_option(P.PFT_OPT_PAIR, 1)
-            L.pft_comm_set_current(None)
-            L.pft_comm_destroy(mine)
-        except BaseException as e:   # noqa: BLE001 -- surfaced below
-            errs.append(e)
-
-    ths = [threading.Thread(target=worker, args=(r,)) for r in range(nprocs)]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join(timeout=600)
-    L.pft_comm_destroy(group)
-    if errs:
-        raise errs[0]
-    return out
+    return run_slabs(nprocs, body, pair=2)                 # the option is per host thread
 
 
 @pytest.mark.parametrize("nprocs", [2, 3, 4])
