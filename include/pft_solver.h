@@ -11,6 +11,7 @@
 
 #include "RK_MPI_SAsolver.h"
 #include "pft_hip.h"
+#include "pft_formula.h"
 #include "pft_io.h"
 
 #ifdef __cplusplus
@@ -57,6 +58,22 @@ int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * lo
    status in as many pft_comm_allgather rounds of at most 256 bytes as that takes (9); the records
    are merged in rank order, every rank returns the same code. */
 int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means * local, pft_means * per_plane);
+
+/* f12: the formula diagnostics (pft_formula.h) of the device-resident x, under the rules of
+   pft_solver_diag word for word: valid after any fused solve or device IC, -3 without an
+   initialised solver or a resident state (never stale numbers), 0 from a Service_Callback on one
+   rank and -2 there with several.  nprog programs (at most PFT_FORMULA_MAX, PFT_FORMULA_MAX_ENTRIES
+   entries in all), program f with lens[f] entries, concatenated in ops / args (pft_frontend.h).
+   Every rank compiles them first (pft_formula_compile) and the ranks agree the outcome before any
+   device work: 1 when a program is not device-exact (nothing is launched: use pft_formula_host), -2
+   for a bad program or limits exceeded, the same on every rank.  global: nprog records of the whole
+   grid, the same bits on every rank; local (optional): this slab's; per_plane (optional, n3 * nprog
+   records): entry f * n3 + k is program f's record of this slab's plane k.  Collective on several
+   ranks: each rank reduces its slab (pft_slab_formulas) and its records travel with its status in
+   pft_comm_allgather rounds of at most 256 bytes; they are merged in rank order and every rank
+   returns the same code. */
+int pft_solver_formulas(int nprog, const int * lens, const int * ops, const double * args, pft_fdiag * global,
+                        pft_fdiag * local, pft_fdiag * per_plane);
 
 /* f1 (after RK_MPI_SA_init): the default Params' initial condition (Params:9-21,
    intertrack.c:1880-2010) and, with with_beads, the glass beads (PrecalculateData,

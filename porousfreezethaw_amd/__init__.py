@@ -165,6 +165,92 @@ class pft_means(C.Structure):
         return d
 
 
+PFT_FORMULA_MAX, PFT_FORMULA_MAX_ENTRIES = 8, 256     # include/pft_formula.h
+FORMULA_INPUTS = ("x", "y", "z", "_x", "_y", "_z", "u", "p", "gl")    # inputs 0..8 of a program (pft_frontend.h)
+FORMULA_ROW_KEYS = ("mean", "sum", "n", "nonzero", "min", "max", "maxabs")   # run_series: <name>_<key>
+
+
+class pft_fdiag(C.Structure):
+    """include/pft_formula.h: the record of one formula over the interior cells -- counts, ordered
+    extrema and the exact sum"""
+    _fields_ = [("cells", C.c_longlong), ("n", C.c_longlong), ("nonzero", C.c_longlong),
+                ("nonfinite", C.c_longlong), ("min", C.c_double), ("max", C.c_double), ("maxabs", C.c_double),
+                ("sum", pft_xsum)]
+
+    def words(self):
+        """the raw words, counts first, the doubles as their bits: equal lists <=> equal records"""
+        bits = np.array([self.min, self.max, self.maxabs], dtype=np.float64).view(np.uint64)
+        return ([int(self.cells), int(self.n), int(self.nonzero), int(self.nonfinite)] + [int(b) for b in bits]
+                + [int(w) for w in self.sum.w])
+
+    def as_dict(self):
+        """cells, n, nonzero, nonfinite, min, max, maxabs, sum (the exact sum rounded once) and mean
+        (the exact quotient sum / n rounded once, NaN when n is 0), as pft_means.values"""
+        d = {k: getattr(self, k) for k in ("cells", "n", "nonzero", "nonfinite", "min", "max", "maxabs")}
+        out = C.c_double()
+        rc = lib().pft_xsum_round(C.byref(self.sum), C.byref(out))
+        if rc:
+            raise RuntimeError(f"pft_xsum_round failed ({rc})")
+        d["sum"] = out.value
+        n, total = int(self.n), self.sum.as_int()
+        if n == 0:
+            d["mean"] = float("nan")
+        else:
+            try:
+                d["mean"] = total / (n << 1074)
+            except OverflowError:
+                d["mean"] = float("inf") if total > 0 else float("-inf")
+        return d
+
+
+def formula_programs(formulas, variables=None):
+    """{name: expression} -> (names, lens, ops, args): the postfix programs of frontend.Evaluator.compile,
+    concatenated for pft_formula_host / pft_solver_formulas.  variables: a {name: value} dict or a
+    frontend.Evaluator whose variables the expressions may use (it is not changed).  The nine node
+    inputs x, y, z, _x, _y, _z, u, p, gl always mean the node's own values, whatever `variables`
+    defines -- the rule of Case.icond_programs.  ValueError (frontend.EvalError is one) for an empty
+    dict, more than PFT_FORMULA_MAX formulas, an undefined symbol, a syntax error or more than
+    PFT_FORMULA_MAX_ENTRIES program entries in all."""
+    from .frontend import VAR, EvalError, Evaluator
+    if not isinstance(formulas, dict) or not formulas:
+        raise ValueError("formulas: a non-empty {name: expression} dict")
+    if len(formulas) > PFT_FORMULA_MAX:
+        raise ValueError(f"formulas: at most {PFT_FORMULA_MAX} per call, not {len(formulas)}")
+    ev = Evaluator()
+    if isinstance(variables, Evaluator):
+        for name, kind, _, value, _ in variables.ident:
+            if kind == VAR:
+                ev.define(name, value)
+    elif variables is not None:
+        for name, value in dict(variables).items():
+            ev.define(str(name), float(value))
+    for v in FORMULA_INPUTS:
+        ev.define(v, 0.5)
+    names, progs = [], []
+    for name, expr in formulas.items():
+        try:
+            prog = ev.compile(str(expr), FORMULA_INPUTS, evaluate=False)
+        except EvalError as e:
+            raise EvalError(f"formula {name!r} ({expr!r}): {e}") from None
+        names.append(str(name))
+        progs.append(prog)
+    if sum(len(pr) for pr in progs) > PFT_FORMULA_MAX_ENTRIES:
+        raise ValueError(f"formulas: the programs have {sum(len(pr) for pr in progs)} entries, more than "
+                         f"{PFT_FORMULA_MAX_ENTRIES}")
+    lens = np.array([len(pr) for pr in progs], dtype=np.int32)
+    ops = np.array([o for pr in progs for o, _ in pr], dtype=np.int32)
+    args = np.array([a for pr in progs for _, a in pr], dtype=np.float64)
+    return names, lens, ops, args
+
+
+class pft_ic_prog(C.Structure):
+    """include/pft_frontend.h: a program compiled for the device (owned by the library: pft_ic_prog_free)"""
+    _fields_ = [("n", C.c_int), ("op", C.POINTER(C.c_int)), ("arg", C.POINTER(C.c_double)), ("ntab", C.c_int),
+                ("tab_axis", C.POINTER(C.c_int)), ("tab_off", C.POINTER(C.c_long)),
+                ("tab_val", C.POINTER(C.c_double)), ("tab_err", C.POINTER(C.c_ubyte)), ("tab_len", C.c_long),
+                ("const_err", C.c_int)]
+
+
 _lib = None
 
 
@@ -262,6 +348,18 @@ def lib():
         L.pft_slab_means_last_ms.argtypes = [C.c_void_p, dp]
         L.pft_solver_means.argtypes = [op, mp, mp, mp]
         L.pft_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        fp, icp = C.POINTER(pft_fdiag), C.POINTER(pft_ic_prog)
+        L.pft_fdiag_init.argtypes = [fp]
+        L.pft_fdiag_init.restype = None
+        L.pft_fdiag_combine.argtypes = [fp, fp]
+        L.pft_formula_host.argtypes = [gp, dp, C.c_int, ip, ip, dp, fp, fp]
+        L.pft_formula_compile.argtypes = [gp, C.c_int, ip, dp, icp]
+        L.pft_ic_prog_free.argtypes = [icp]
+        L.pft_ic_prog_free.restype = None
+        L.pft_slab_formulas.argtypes = [C.c_void_p, C.c_int, C.c_int, icp, fp, fp]
+        L.pft_slab_formulas_timing.argtypes = [C.c_void_p, C.c_int]
+        L.pft_slab_formulas_last_ms.argtypes = [C.c_void_p, dp]
+        L.pft_solver_formulas.argtypes = [C.c_int, ip, ip, dp, fp, fp, fp]
         rp, vpp = C.POINTER(pft_snapshot_ranges), C.POINTER(C.c_void_p)
         L.pft_snapshot_image_bytes.argtypes = [gp]
         L.pft_snapshot_image_bytes.restype = C.c_size_t
@@ -718,6 +816,110 @@ class Simulation:
             d["plane_records"] = planes
         return d
 
+    # -- f12: formula diagnostics ------------------------------------------------------------------
+    def _formulas_host_global(self, progs, planes):
+        """pft_formula_host of self.x, merged over the communicator's ranks in rank order (collective;
+        the records travel in pft_comm_allgather rounds of at most 256 bytes)"""
+        L_ = self.lib
+        names, lens, ops, args = progs
+        nprog = len(names)
+        mine = (pft_fdiag * nprog)()
+        rc = L_.pft_formula_host(C.byref(self.grid), _dp(self.x), nprog, _ip(lens), _ip(ops), _dp(args), mine, planes)
+        if rc:
+            raise RuntimeError(f"pft_formula_host failed ({rc})")
+        comm = L_.pft_comm_current()
+        n = L_.pft_comm_size(comm) if comm else 1
+        if n == 1:
+            return mine, mine
+        raw, size = bytes(mine), C.sizeof(mine)
+        parts = [bytearray() for _ in range(n)]
+        for off in range(0, size, 256):
+            piece = raw[off:off + 256]
+            every = C.create_string_buffer(n * len(piece))
+            rc = L_.pft_comm_allgather(comm, piece, len(piece), every)
+            if rc:
+                raise RuntimeError(f"pft_comm_allgather failed ({rc})")
+            for r in range(n):
+                parts[r] += every.raw[r * len(piece):(r + 1) * len(piece)]
+        glob = (pft_fdiag * nprog).from_buffer_copy(bytes(parts[0]))
+        for r in range(1, n):
+            other = (pft_fdiag * nprog).from_buffer_copy(bytes(parts[r]))
+            for f in range(nprog):
+                L_.pft_fdiag_combine(C.byref(glob[f]), C.byref(other[f]))
+        return glob, mine
+
+    def formulas(self, formulas, variables=None, where="device", per_plane=False):
+        """f12: named formulas of the parameter file's language over the node inputs x, y, z, _x, _y,
+        _z, u, p, gl and `variables` (a {name: value} dict or a frontend.Evaluator; the nine inputs
+        always mean the node's own values), evaluated at every interior cell of the whole grid and
+        reduced exactly (include/pft_formula.h).  Returns {name: dict} with cells, n, nonzero,
+        nonfinite, min, max, maxabs, sum and mean -- the same bits on any decomposition.
+        where="device": of the device-resident state, by pft_solver_formulas -- no download;
+        collective on several ranks; RuntimeError when nothing is resident; ValueError naming the
+        formula when one is not device-exact (pow or a libm function, C or P over a field or several
+        coordinates, a deep stack: use where="host").  where="host": pft_formula_host of self.x,
+        merged over the ranks (collective too); it accepts every formula.  per_plane: each dict
+        also has <name>_profile, the means of this rank's planes (global rows first_row + k),
+        first_row, "local", this slab's own scalars, and "record" / "plane_records", the raw
+        pft_fdiag structs.  ValueError (frontend.EvalError is one) before any work for an undefined
+        symbol, an empty dict, more than 8 formulas or programs of more than 256 entries."""
+        if where not in ("device", "host"):
+            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
+        progs = formula_programs(formulas, variables)
+        d = self._formulas(progs, where, per_plane)
+        if d is None:
+            raise RuntimeError("formulas: no state is resident on the device (no initialised solver, or no "
+                               "fused solve or device IC yet); solve first, or use where='host'")
+        return d
+
+    def _formula_not_exact(self, progs):
+        """the name of the first formula that does not compile for the device, or None"""
+        names, lens, ops, args = progs
+        off = 0
+        for name, n in zip(names, lens):
+            pr = pft_ic_prog()
+            rc = self.lib.pft_formula_compile(C.byref(self.grid), int(n), _ip(ops[off:off + n].copy()),
+                                              _dp(args[off:off + n].copy()), C.byref(pr))
+            self.lib.pft_ic_prog_free(C.byref(pr))
+            if rc:
+                return name
+            off += int(n)
+        return None
+
+    def _formulas(self, progs, where, per_plane):
+        """formulas() on compiled programs (formula_programs); None when where="device" and nothing
+        is resident (pft_solver_formulas' -3, the same on every rank)"""
+        names, lens, ops, args = progs
+        nprog, n3 = len(names), self.grid.n3
+        planes = (pft_fdiag * (n3 * nprog))() if per_plane else None
+        if where == "host":
+            glob, mine = self._formulas_host_global(progs, planes)
+        else:
+            glob, mine = (pft_fdiag * nprog)(), (pft_fdiag * nprog)()
+            rc = self.lib.pft_solver_formulas(nprog, _ip(lens), _ip(ops), _dp(args), glob, mine, planes)
+            if rc == -3:
+                return None
+            if rc == 1:
+                raise ValueError(f"formulas: {self._formula_not_exact(progs)!r} is not device-exact (pow or a libm "
+                                 "function, C or P over a field or several coordinates, or a stack deeper than "
+                                 "the device's); use where='host'")
+            if rc == -2:
+                raise ValueError("formulas: pft_solver_formulas refused the programs (-2)")
+            if rc:
+                raise RuntimeError(f"pft_solver_formulas failed ({rc}): {self.lib.pft_hip_last_error()}")
+        out = {}
+        for f, name in enumerate(names):
+            d = glob[f].as_dict()
+            if per_plane:
+                mine_planes = [planes[f * n3 + k] for k in range(n3)]
+                d[name + "_profile"] = np.array([m.as_dict()["mean"] for m in mine_planes], dtype=np.float64)
+                d["first_row"] = self.grid.first_row
+                d["local"] = mine[f].as_dict()
+                d["record"] = glob[f]
+                d["plane_records"] = mine_planes
+            out[name] = d
+        return out
+
     # -- f7: snapshots from the resident state -----------------------------------------------------
     def _region(self, sel):
         """the pft_region of a selection (region()) on this simulation's grid; a pft_region is checked"""
@@ -817,7 +1019,7 @@ class Simulation:
     def run_series(self, final_time=None, saved_files=None, times=None, snapshot_path=None, comment="",
                    diag=True, opts=None, means=False, snapshot_where="host", snapshot_async=False,
                    first_snapshot=0, total_snapshots=None, skip_first=False, regions=None, region_every=1,
-                   snapshot_full=True):
+                   snapshot_full=True, formulas=None, variables=None):
         """The driver's snapshot loop (intertrack.c:2265-2283).  Snapshot 0 is the state as it
         stands (no solve); snapshot s solves to series_times(t0, final_time, saved_files)[s], or
         to times[s - 1] when times= lists the solve targets.  The steps run device-resident
@@ -840,7 +1042,29 @@ class Simulation:
         regions={"xz": sel, ...} (f11; sel: see region()): each named region is written as the region
         dataset "<snapshot_path>.<name>.%03d.ncd" at every snapshot whose number is a multiple of
         region_every, by the route of snapshot_where and snapshot_async; snapshot_full=False leaves
-        the full datasets out altogether.  The rows do not depend on any of it."""
+        the full datasets out altogether.  The rows do not depend on any of it.
+        formulas={name: expression} (f12; variables: see formulas(); or formula_programs()' result, compiled
+        already): every row also carries
+        <name>_mean, _sum, _n, _nonzero, _min, _max and _maxabs of each formula over the whole grid, from
+        the device-resident state, so that write_series_txt(rows, path, key="<name>_mean") writes its
+        series.  The programs are compiled once, before the first solve; ValueError up front for a
+        formula that is not device-exact and for a name whose keys would collide with a key of
+        diagnostics() or means()."""
+        progs = None
+        if formulas is not None:
+            # (a tuple: programs compiled already by formula_programs, as Case.run passes them)
+            progs = formulas if isinstance(formulas, tuple) else formula_programs(formulas, variables)
+            taken = ({"snapshot", "t", "h", "steps", "steps_total", "rc", "ice_fraction"}
+                     | {k for k, _ in pft_diag._fields_} | {k + s for k in MEAN_KEYS for s in ("_n", "_sum", "_mean")})
+            keys = [name + "_" + k for name in progs[0] for k in FORMULA_ROW_KEYS]
+            clash = sorted(set(keys) & taken) + sorted({k for k in keys if keys.count(k) > 1})
+            if clash:
+                raise ValueError(f"run_series: the formula keys {clash} collide with keys of diagnostics(), "
+                                 "means() or another formula; rename the formula")
+            bad = self._formula_not_exact(progs)
+            if bad is not None:
+                raise ValueError(f"run_series: formula {bad!r} is not device-exact; evaluate it with "
+                                 "formulas(where='host') on a downloaded state")
         region_every = int(region_every)
         if region_every < 1:
             raise ValueError(f"region_every must be at least 1, not {region_every}")
@@ -867,14 +1091,15 @@ class Simulation:
         rows = []
         try:
             rows = self._run_series(targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
-                                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full)
+                                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full,
+                                    progs)
         finally:
             if self._snap_pending:
                 self.snapshot_wait()
         return rows
 
     def _run_series(self, targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
-                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full):
+                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full, progs=None):
         rows = []
         for s, T in enumerate(targets, first):
             rc = None
@@ -899,6 +1124,15 @@ class Simulation:
                     raise RuntimeError("run_series: no state is resident on the device after the solve "
                                        "(the host-staged path keeps none)")
                 row.update(d)
+            if progs is not None:
+                d = self._formulas(progs, "device", False)
+                if d is None and s == first:
+                    d = self._formulas(progs, "host", False)
+                if d is None:
+                    raise RuntimeError("run_series: no state is resident on the device after the solve "
+                                       "(the host-staged path keeps none)")
+                for name, rec in d.items():
+                    row.update({name + "_" + k: rec[k] for k in FORMULA_ROW_KEYS})
             if snapshot_path is not None and not (s == first and skip_first):
                 info = snapshot_info(self.system.t, self.system.h, end, self.system.delta, self.grid.calc_mode,
                                      snapshot=s, total_snapshots=total, comment=comment)

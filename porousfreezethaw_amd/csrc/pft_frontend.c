@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "../../include/pft_frontend.h"
+#include "pft_ic_nodes.h"
 #include "pft_ic_ops.h"
 
 #define STACK 64
@@ -145,30 +146,34 @@ static int validate(int n, const int * op, const double * arg)
 	return (depth != 1 || maxdepth > STACK) ? -2 : 0;
 }
 
+int pft_ic_validate(int n, const int * op, const double * arg)
+{
+	return validate(n, op, arg);
+}
+
+double pft_ic_run_host(int n, const int * op, const double * arg, const double * in, int * err)
+{
+	return run_e(n, op, arg, in, err);
+}
+
+typedef struct { int q, n; const int * op; const double * arg; double * w; long S; } ic_eval_ctx;
+
+static void ic_eval_node(void * ctx, long idx, double * in)
+{
+	const ic_eval_ctx * c = (const ic_eval_ctx *)ctx;
+	in[6] = c->w[idx]; in[7] = c->w[c->S + idx]; in[8] = c->w[2*c->S + idx];
+	c->w[c->q*c->S + idx] = run(c->n, c->op, c->arg, in);
+}
+
 int pft_ic_eval(const pft_grid * g, int q, int n, const int * op, const double * arg, double * w)
 {
-	const long N1 = g->n1 + 2*PFT_BCOND_THICKNESS, N2 = g->n2 + 2*PFT_BCOND_THICKNESS;
-	const long N3 = g->n3 + 2*PFT_BCOND_THICKNESS, S = N1*N2*N3;
+	ic_eval_ctx c;
 	int k;
 	if(!g || !w || q < 0 || q > 2 || validate(n, op, arg)) return -2;
+	c.q = q; c.n = n; c.op = op; c.arg = arg; c.w = w;
+	c.S = (long)(g->n1 + 2*PFT_BCOND_THICKNESS) * (g->n2 + 2*PFT_BCOND_THICKNESS) * (g->n3 + 2*PFT_BCOND_THICKNESS);
 	#pragma omp parallel for schedule(static)
-	for(k = 0; k < g->n3; k++) {
-		double in[9];
-		int j, ii;
-		const double _z = (0.5 + k + g->first_row) / g->total_n3;    /* intertrack.c:1958-1960 */
-		in[5] = _z; in[2] = g->L3 * _z;
-		for(j = 0; j < g->n2; j++) {
-			const double _y = (0.5 + j) / g->n2;
-			in[4] = _y; in[1] = g->L2 * _y;
-			for(ii = 0; ii < g->n1; ii++) {
-				const long idx = (k + PFT_BCOND_THICKNESS)*N1*N2 + (j + PFT_BCOND_THICKNESS)*N1 + ii + PFT_BCOND_THICKNESS;
-				const double _x = (0.5 + ii) / g->n1;
-				in[3] = _x; in[0] = g->L1 * _x;
-				in[6] = w[idx]; in[7] = w[S + idx]; in[8] = w[2*S + idx];
-				w[q*S + idx] = run(n, op, arg, in);
-			}
-		}
-	}
+	for(k = 0; k < g->n3; k++) pft_ic_plane_nodes(g, k, ic_eval_node, &c);   /* the loop f12 shares */
 	return 0;
 }
 

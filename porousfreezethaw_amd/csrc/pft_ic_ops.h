@@ -1,7 +1,8 @@
 /*
  * pft_ic_ops.h -- the operators of a compiled `icond` program that the device evaluates bit for bit
  * as the host does (f1, general formulas: pft_ic_compile in pft_frontend.c, ic_prog_kernel in
- * pft_kernels.hip).  Compiled both as C (the host restatement pft_ic_prog_eval_host that the CPU
+ * pft_kernels.hip; f12, formula diagnostics: formula_kernel in pft_reduce.hip, which never meets
+ * C or P -- pft_formula_compile).  Compiled both as C (the host restatement pft_ic_prog_eval_host that the CPU
  * tests compare with pft_ic_eval) and as HIP device code; always without contraction.
  *
  * Each operator is the reference evaluator's handler (exp_all.cc:21-250, ee_wrapper.cc:255-301) as
@@ -39,9 +40,16 @@ static inline PFT_HD double pft_ic_binary(int op, double x, double y, int * e)
 		case 3: return x * y;
 		case 4: if(y == 0) { *e = 1; return 0; } return x / y;
 		case 5: case 6:                                         /* C, P (exp_all.cc:223-239) */
+#ifdef PFT_IC_NO_CP
+			/* f12's device interpreter (pft_reduce.hip): the loop below runs as often as the
+			   operand says, so it is not compiled there at all; pft_formula_compile keeps C and P
+			   out of its programs and pft_slab_formulas refuses them */
+			*e = 1; return 0;
+#else
 			if(x < 0 || x != floor(x) || y < 0 || y != floor(y) || x < y) { *e = 1; return 0; }
 			while(y) { r *= x--; if(op == 5) r /= y; y--; }
 			return r;
+#endif
 		case 9: return x > y ? x : y;                           /* max */
 		case 10: return x < y ? x : y;                          /* min */
 		case 11: return x < y ? 1 : 0;

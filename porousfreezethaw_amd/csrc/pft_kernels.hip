@@ -2553,6 +2553,12 @@ int pft_slab_destroy(pft_slab* s)
   if (s->means_host) (void)hipHostFree(s->means_host);
   for (int i = 0; i < 2; ++i)
     if (s->ev_means[i]) (void)hipEventDestroy(s->ev_means[i]);
+  if (s->formula_dev) (void)hipFree(s->formula_dev);
+  if (s->formula_host) (void)hipHostFree(s->formula_host);
+  if (s->formula_prog_dev) (void)hipFree(s->formula_prog_dev);
+  if (s->formula_prog_host) (void)hipHostFree(s->formula_prog_host);
+  for (int i = 0; i < 2; ++i)
+    if (s->ev_formula[i]) (void)hipEventDestroy(s->ev_formula[i]);
   if (s->snap_host) {
     // the background writer may still read the image: it finishes first
     (void)pft_snapshot_writer_release(s->snap_host);

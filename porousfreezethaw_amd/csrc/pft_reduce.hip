@@ -1,6 +1,11 @@
 // pft_reduce.hip -- reductions over the resident state: the ice diagnostics (diag_kernel, f5) and
-// the exact means and z-profiles (means_kernel, f6), with their host API.
+// the exact means and z-profiles (means_kernel, f6), and the formula diagnostics (formula_kernel,
+// f12), with their host API.
 #include "pft_slab.h"
+
+#include "../../include/pft_formula.h"
+#define PFT_IC_NO_CP   // no loop with a cell's value as its trip count is compiled into formula_kernel
+#include "pft_ic_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -348,17 +353,22 @@ __device__ __forceinline__ long long means_wave_sum(long long v)
 }
 
 // the wave's registers into the workgroup's LDS record: s_all / s_msk point at the two sums' words
+// (MASKED = false: one value stream into one pft_xsum -- no masked sum, s_msk is not touched; f12)
+template <bool MASKED = true>
 __device__ __forceinline__ void means_flush(MeansPair& st, int lane, unsigned long long* s_all, unsigned long long* s_msk)
 {
   const long long a0 = means_wave_sum(st.a0), a1 = means_wave_sum(st.a1), a2 = means_wave_sum(st.a2);
-  const long long m0 = means_wave_sum(st.m0), m1 = means_wave_sum(st.m1), m2 = means_wave_sum(st.m2);
+  const long long m0 = MASKED ? means_wave_sum(st.m0) : 0, m1 = MASKED ? means_wave_sum(st.m1) : 0,
+                  m2 = MASKED ? means_wave_sum(st.m2) : 0;
   if (lane == 0) {
     if (a0) atomicAdd(&s_all[st.cur], (unsigned long long)a0);
     if (a1) atomicAdd(&s_all[st.cur + 1], (unsigned long long)a1);
     if (a2) atomicAdd(&s_all[st.cur + 2], (unsigned long long)a2);
-    if (m0) atomicAdd(&s_msk[st.cur], (unsigned long long)m0);
-    if (m1) atomicAdd(&s_msk[st.cur + 1], (unsigned long long)m1);
-    if (m2) atomicAdd(&s_msk[st.cur + 2], (unsigned long long)m2);
+    if (MASKED) {
+      if (m0) atomicAdd(&s_msk[st.cur], (unsigned long long)m0);
+      if (m1) atomicAdd(&s_msk[st.cur + 1], (unsigned long long)m1);
+      if (m2) atomicAdd(&s_msk[st.cur + 2], (unsigned long long)m2);
+    }
   }
   st.a0 = st.a1 = st.a2 = st.m0 = st.m1 = st.m2 = 0;
 }
@@ -387,8 +397,9 @@ __device__ __forceinline__ void means_signed_digits(double x, bool act, long lon
 }
 
 // the eight values x[] of a wave's iteration (v: the slot exists, msk: it enters the masked sum)
-// into st; n_all / n_msk: the wave-uniform counts of the cells that entered
-template <int NE, int I0, int I1>
+// into st; n_all / n_msk: the wave-uniform counts of the cells that entered.  MASKED = false: the
+// one-stream form of f12 -- msk, n_msk and s_msk are ignored and the m registers stay zero
+template <int NE, int I0, int I1, bool MASKED = true>
 __device__ __forceinline__ void means_accumulate(MeansPair& st, const double (&x)[NE], const bool (&v)[NE],
                                                  const bool (&msk)[NE], unsigned long long& n_all,
                                                  unsigned long long& n_msk, int lane, unsigned long long* s_all,
@@ -405,7 +416,7 @@ __device__ __forceinline__ void means_accumulate(MeansPair& st, const double (&x
     act[i] = fin && (bits << 1) != 0;            // finite and not +-0
     c[i] = ((E > 1 ? E : 1) - 1) >> 5;
     n_all += __popcll(__ballot(fin));
-    n_msk += __popcll(__ballot(fin && msk[i]));
+    if (MASKED) n_msk += __popcll(__ballot(fin && msk[i]));
     other |= act[i] && c[i] != st.cur;
     minus |= act[i] && (bits >> 63) != 0;
   }
@@ -419,7 +430,7 @@ __device__ __forceinline__ void means_accumulate(MeansPair& st, const double (&x
       bool neg;
       means_digits(x[i], act[i], e0, e1, e2, neg);
       st.a0 += e0, st.a1 += e1, st.a2 += e2;
-      st.m0 += msk[i] ? e0 : 0u, st.m1 += msk[i] ? e1 : 0u, st.m2 += msk[i] ? e2 : 0u;
+      if (MASKED) st.m0 += msk[i] ? e0 : 0u, st.m1 += msk[i] ? e1 : 0u, st.m2 += msk[i] ? e2 : 0u;
     }
     return;
   }
@@ -430,7 +441,7 @@ __device__ __forceinline__ void means_accumulate(MeansPair& st, const double (&x
       long long d0, d1, d2;
       means_signed_digits(x[i], act[i], d0, d1, d2);
       st.a0 += d0, st.a1 += d1, st.a2 += d2;
-      st.m0 += msk[i] ? d0 : 0, st.m1 += msk[i] ? d1 : 0, st.m2 += msk[i] ? d2 : 0;
+      if (MASKED) st.m0 += msk[i] ? d0 : 0, st.m1 += msk[i] ? d1 : 0, st.m2 += msk[i] ? d2 : 0;
     }
     return;
   }
@@ -439,19 +450,19 @@ __device__ __forceinline__ void means_accumulate(MeansPair& st, const double (&x
     const unsigned long long m_act = __ballot(act[i]);
     if (!m_act) continue;
     if (!__ballot(act[i] && c[i] == st.cur)) {
-      means_flush(st, lane, s_all, s_msk);
+      means_flush<MASKED>(st, lane, s_all, s_msk);
       st.cur = __builtin_amdgcn_readfirstlane(__shfl(c[i], (int)__ffsll((long long)m_act) - 1, 64));
     }
     long long d0, d1, d2;
     means_signed_digits(x[i], act[i], d0, d1, d2);
     const bool here = c[i] == st.cur;            // (inactive lanes: zero digits, either way nothing)
     st.a0 += here ? d0 : 0, st.a1 += here ? d1 : 0, st.a2 += here ? d2 : 0;
-    st.m0 += here && msk[i] ? d0 : 0, st.m1 += here && msk[i] ? d1 : 0, st.m2 += here && msk[i] ? d2 : 0;
+    if (MASKED) st.m0 += here && msk[i] ? d0 : 0, st.m1 += here && msk[i] ? d1 : 0, st.m2 += here && msk[i] ? d2 : 0;
     if (act[i] && !here) {
       if (d0) atomicAdd(&s_all[c[i]], (unsigned long long)d0);
       if (d1) atomicAdd(&s_all[c[i] + 1], (unsigned long long)d1);
       if (d2) atomicAdd(&s_all[c[i] + 2], (unsigned long long)d2);
-      if (msk[i]) {
+      if (MASKED && msk[i]) {
         if (d0) atomicAdd(&s_msk[c[i]], (unsigned long long)d0);
         if (d1) atomicAdd(&s_msk[c[i] + 1], (unsigned long long)d1);
         if (d2) atomicAdd(&s_msk[c[i] + 2], (unsigned long long)d2);
@@ -647,6 +658,428 @@ int pft_slab_means_last_ms(pft_slab* s, double* ms)
   if (!s || !ms || !s->means_timing) return -2;
   float f = 0.0f;
   HIPCHK(hipEventElapsedTime(&f, s->ev_means[0], s->ev_means[1]));
+  *ms = f;
+  return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// f12: formula diagnostics (pft_formula.h) -- means_kernel's traversal (work items are segments of
+// one interior plane, 16-byte loads, per iteration a wave takes 512 consecutive elements), but the
+// value of a cell comes from a compiled program (pft_formula_compile) that the wave interprets:
+// the program counter, the operator codes, the constants and the table descriptors are
+// wave-uniform and read through read-only kernel-argument pointers (scalar loads), the operators
+// are those of csrc/pft_ic_ops.h -- the host's -- and the evaluation stack is a per-lane column in
+// LDS, st[slot * 256 + tid] (15 slots, 30 KiB per workgroup, every lane its own bank pair), with
+// the top of the stack in a register: a runtime-indexed double st[16] would live in scratch.
+// blockIdx.y is the program; each program re-reads the state (a field it never pushes is not
+// loaded).  The reductions are integers only: counts by ballot and popcount, min / max through
+// diag_key and maxabs through the bits of |v| (64-bit integer atomic max), the sum through
+// means_accumulate in its one-stream form -- formula values have any sign and exponent, so its
+// signed and per-lane paths are the usual ones here.  A plane's record (FD_REC words) is gathered
+// in LDS per work item and added to the plane's record in global memory; formula_total_kernel
+// combines the planes' records into the slab's.
+//
+// No loop here depends on a cell's value but the factorial's, bounded at 170: C and P never reach
+// the device (pft_formula_compile; pft_slab_formulas refuses them), and their loop is not even
+// compiled into this file (PFT_IC_NO_CP above).  After a math error a lane goes on through the
+// remaining entries -- the program counter is the wave's -- and yields 0 at the end, the value
+// pft_ic_run returns at once.
+enum { FD_N = 0, FD_NONZERO, FD_NONFINITE, FD_MAX, FD_MIN, FD_MAXABS, FD_SUM, FD_REC = FD_SUM + PFT_XSUM_WORDS };
+#define PFT_FORMULA_SLOTS (PFT_IC_STACK - 1)   // LDS slots: the top of the stack is a register
+enum { FM_NEED_U = 1, FM_NEED_P = 2, FM_NEED_GL = 4, FM_NEED_IJ = 8 };
+
+// the programs of one call, all in one device blob.  code[c] = {op, aux}: 100 push arg[c]; 101 push
+// the node's field aux (0 u, 1 p, 2 gl); 102 / 103 / 104 push entry aux + i / j / k of tval (its
+// math-error flag in terr); the operators of pft_ic_ops.h.  meta[3 f ..]: program f's first entry,
+// the entry past its last, its FM_NEED_* bits.
+struct FormulaProgs {
+  const int2* __restrict__ code;
+  const double* __restrict__ arg;
+  const double* __restrict__ tval;
+  const unsigned char* __restrict__ terr;
+  const int* __restrict__ meta;
+};
+
+// pft_ic_run's semantics at one node: entries [c0, c1), st this lane's LDS column
+__device__ __forceinline__ double formula_eval(const FormulaProgs& P, int c0, int c1, double u, double p, double g,
+                                               int i, int j, int k, double* st)
+{
+  double top = 0.0;
+  int sp = 0, err = 0;
+  for (int c = c0; c < c1; ++c) {
+    const int2 cd = P.code[c];
+    const int o = cd.x;
+    if (o >= 100) {
+      double v;
+      if (o == 100)
+        v = P.arg[c];
+      else if (o == 101)
+        v = cd.y == 0 ? u : (cd.y == 1 ? p : g);
+      else {
+        const int x = cd.y + (o == 102 ? i : (o == 103 ? j : k));
+        err |= P.terr[x];
+        v = P.tval[x];
+      }
+      if (sp > 0) st[(sp - 1) * PFT_DBLOCK] = top;
+      top = v;
+      ++sp;
+    } else if (o < 20) {
+      --sp;
+      top = pft_ic_binary(o, st[(sp - 1) * PFT_DBLOCK], top, &err);
+    } else {
+      top = pft_ic_unary(o, top, &err);
+    }
+  }
+  return err ? 0.0 : top;   // a math error anywhere yields 0, as the reference's Eval()
+}
+
+struct FormulaState {
+  MeansPair sum;
+  unsigned long long n, nonzero, nonfinite;   // wave-uniform counts
+  unsigned long long kmax, kmin, kabs;        // per-lane keys (0: no value yet)
+};
+
+// one iteration of a wave: elements r0 .. r0 + 511 of the item's pair-aligned frame (of them
+// [r_lo, r_hi) belong to the item, element r_lo being element `first` of plane k; FULL: all do)
+template <bool FULL>
+__device__ __forceinline__ void formula_iter(FormulaState& st, const FormulaProgs& P, int c0, int c1, int need,
+                                             const double* __restrict__ fu, const double* __restrict__ fp,
+                                             const double* __restrict__ fg, int r0, int r_lo, int r_hi, int first,
+                                             int n1, int k, int lane, double* stack, unsigned long long* s_sum)
+{
+#pragma unroll 1
+  for (int jj = 0; jj < PFT_DIAG_UNROLL; ++jj) {
+    const int r = r0 + 128 * jj + 2 * lane;
+    double u[2] = {0.0, 0.0}, p[2] = {0.0, 0.0}, g[2] = {0.0, 0.0}, x[2];
+    bool v[2];
+    if (FULL) {
+      if (need & FM_NEED_U) {
+        const double2 a = *reinterpret_cast<const double2*>(fu + r);
+        u[0] = a.x, u[1] = a.y;
+      }
+      if (need & FM_NEED_P) {
+        const double2 a = *reinterpret_cast<const double2*>(fp + r);
+        p[0] = a.x, p[1] = a.y;
+      }
+      if (need & FM_NEED_GL) {
+        const double2 a = *reinterpret_cast<const double2*>(fg + r);
+        g[0] = a.x, g[1] = a.y;
+      }
+      v[0] = v[1] = true;
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const bool ok = r + h >= r_lo && r + h < r_hi;
+        v[h] = ok;
+        if (ok && (need & FM_NEED_U)) u[h] = fu[r + h];
+        if (ok && (need & FM_NEED_P)) p[h] = fp[r + h];
+        if (ok && (need & FM_NEED_GL)) g[h] = fg[r + h];
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      // the node's place in its plane; a slot outside the item evaluates node 0 (inside every
+      // table) and is left out of every count below
+      const int e = v[h] ? first + (r + h - r_lo) : 0;
+      int i = 0, j = 0;
+      if (need & FM_NEED_IJ) {
+        j = e / n1;
+        i = e - j * n1;
+      }
+      x[h] = formula_eval(P, c0, c1, u[h], p[h], g[h], i, j, k, stack);
+      st.nonzero += __popcll(__ballot(v[h] && x[h] != 0));          // (a NaN is "true")
+      st.nonfinite += __popcll(__ballot(v[h] && !diag_finite(x[h])));
+      if (v[h] && x[h] == x[h]) {
+        const unsigned long long key = diag_key(x[h]);
+        const unsigned long long a = (unsigned long long)__double_as_longlong(fabs(x[h]));
+        st.kmax = key > st.kmax ? key : st.kmax;
+        st.kmin = ~key > st.kmin ? ~key : st.kmin;
+        st.kabs = a > st.kabs ? a : st.kabs;   // non-negative doubles (and +Inf) order as their bits
+      }
+    }
+    unsigned long long unused = 0;
+    means_accumulate<2, 0, 2, false>(st.sum, x, v, v, st.n, unused, lane, s_sum, s_sum);
+  }
+}
+
+// rec: PFT_FORMULA_MAX total records (written by formula_total_kernel), then for program f the
+// records of its n3 planes from record PFT_FORMULA_MAX + f * n3
+__global__ __launch_bounds__(PFT_DBLOCK) void formula_kernel(const double* __restrict__ fu, const double* __restrict__ fp,
+                                                             const double* __restrict__ fg, int plane, int head, int n1,
+                                                             int n3, int segs, int seg_len, FormulaProgs P,
+                                                             unsigned long long* __restrict__ rec)
+{
+  __shared__ double s_stack[PFT_FORMULA_SLOTS * PFT_DBLOCK];
+  __shared__ unsigned long long s_rec[FD_REC];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int f = blockIdx.y;
+  const int c0 = P.meta[3 * f], c1 = P.meta[3 * f + 1], need = P.meta[3 * f + 2];
+  for (int i = threadIdx.x; i < FD_REC; i += PFT_DBLOCK) s_rec[i] = 0;
+  __syncthreads();
+  FormulaState st;
+  st.sum.a0 = st.sum.a1 = st.sum.a2 = st.sum.m0 = st.sum.m1 = st.sum.m2 = 0;
+  st.sum.cur = 32;
+  double* stack = s_stack + threadIdx.x;
+  unsigned long long* planes = rec + (size_t)(PFT_FORMULA_MAX + (size_t)f * n3) * FD_REC;
+  const long items = (long)n3 * segs;
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    const int k = (int)(item / segs), j = (int)(item - (long)k * segs);
+    const int first = j * seg_len;                                    // within the plane
+    const int len = plane - first < seg_len ? plane - first : seg_len;
+    const long a = (long)k * plane + first;                           // within the run of n3 planes
+    // the frame of means_kernel: e_base on a 16-byte boundary at or one below a
+    const long e_base = 2 * ((a + head) >> 1) - head;
+    const int r_lo = (int)(a - e_base), r_hi = r_lo + len;
+    const int span = (r_hi + 1) & ~1;
+    const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
+    const double* wp = fp + e_base;
+    const double* wg = fg + e_base;
+    st.n = st.nonzero = st.nonfinite = 0;
+    st.kmax = st.kmin = st.kabs = 0;
+    for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
+      if (r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi)
+        formula_iter<true>(st, P, c0, c1, need, wu, wp, wg, r0, r_lo, r_hi, first, n1, k, lane, stack, s_rec + FD_SUM);
+      else
+        formula_iter<false>(st, P, c0, c1, need, wu, wp, wg, r0, r_lo, r_hi, first, n1, k, lane, stack, s_rec + FD_SUM);
+    }
+    means_flush<false>(st.sum, lane, s_rec + FD_SUM, s_rec + FD_SUM);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      unsigned long long o;
+      o = __shfl_xor(st.kmax, off, 64), st.kmax = o > st.kmax ? o : st.kmax;
+      o = __shfl_xor(st.kmin, off, 64), st.kmin = o > st.kmin ? o : st.kmin;
+      o = __shfl_xor(st.kabs, off, 64), st.kabs = o > st.kabs ? o : st.kabs;
+    }
+    if (lane == 0) {
+      if (st.n) atomicAdd(&s_rec[FD_N], st.n);
+      if (st.nonzero) atomicAdd(&s_rec[FD_NONZERO], st.nonzero);
+      if (st.nonfinite) atomicAdd(&s_rec[FD_NONFINITE], st.nonfinite);
+      if (st.kmax) atomicMax(&s_rec[FD_MAX], st.kmax);
+      if (st.kmin) atomicMax(&s_rec[FD_MIN], st.kmin);
+      if (st.kabs) atomicMax(&s_rec[FD_MAXABS], st.kabs);
+    }
+    __syncthreads();
+    // one thread per word: the non-zero ones to the plane's record, and the LDS copy zeroed again
+    unsigned long long* dst = planes + (size_t)k * FD_REC;
+    for (int i = threadIdx.x; i < FD_REC; i += PFT_DBLOCK) {
+      const unsigned long long x = s_rec[i];
+      if (x) {
+        if (i >= FD_MAX && i <= FD_MAXABS)
+          atomicMax(&dst[i], x);
+        else
+          atomicAdd(&dst[i], x);
+        s_rec[i] = 0;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// program blockIdx.y's slab record = its planes' records combined word by word (counts and sum
+// words add, keys take the maximum): per word four threads, each a quarter of the planes, then one
+// of them stores the result (no atomics: nobody else writes the total records)
+__global__ __launch_bounds__(256) void formula_total_kernel(unsigned long long* __restrict__ rec, int n3)
+{
+  __shared__ unsigned long long s_part[4][64];
+  const int l = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int w = blockIdx.x * 64 + l, f = blockIdx.y;
+  const bool is_key = w >= FD_MAX && w <= FD_MAXABS;
+  const unsigned long long* planes = rec + (size_t)(PFT_FORMULA_MAX + (size_t)f * n3) * FD_REC;
+  unsigned long long x = 0;
+  if (w < FD_REC)
+    for (int k = q; k < n3; k += 4) {
+      const unsigned long long o = planes[(size_t)k * FD_REC + w];
+      x = is_key ? (o > x ? o : x) : x + o;
+    }
+  s_part[q][l] = x;
+  __syncthreads();
+  if (q == 0 && w < FD_REC) {
+    for (int i = 1; i < 4; ++i) {
+      const unsigned long long o = s_part[i][l];
+      x = is_key ? (o > x ? o : x) : x + o;
+    }
+    rec[(size_t)f * FD_REC + w] = x;
+  }
+}
+
+// a device record's words as a pft_fdiag of `cells` cells
+static void formula_record(const unsigned long long* h, long long cells, pft_fdiag* out)
+{
+  const double inf = __builtin_inf();
+  out->cells = cells;
+  out->n = (long long)h[FD_N];
+  out->nonzero = (long long)h[FD_NONZERO];
+  out->nonfinite = (long long)h[FD_NONFINITE];
+  out->max = h[FD_MAX] ? diag_unkey(h[FD_MAX]) : -inf;
+  out->min = h[FD_MIN] ? diag_unkey(~h[FD_MIN]) : inf;
+  memcpy(&out->maxabs, &h[FD_MAXABS], 8);
+  memcpy(out->sum.w, h + FD_SUM, sizeof(out->sum.w));
+}
+
+extern "C" {
+
+int pft_slab_formulas(pft_slab* s, int buf, int nprog, const pft_ic_prog* progs, pft_fdiag* total, pft_fdiag* per_plane)
+{
+  if (!s || !progs || !total || buf < 0 || buf >= PFT_BUF_COUNT || nprog < 1 || nprog > PFT_FORMULA_MAX) return -2;
+  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_formulas");
+  const long plane = s->plane, n = (long)s->d.n3 * plane;
+  const int n3 = s->d.n3;
+  if (n > 0x7fffffffL || plane > PFT_MEANS_MAX_PLANE) return -2;
+  // every program checked before anything is launched: only what the device runs exactly and in
+  // bounded time (else 1: not device-exact), a stack within the LDS column (else 1), a well-formed
+  // program with tables of this slab's grid (else -2)
+  long entries = 0, tvals = 0;
+  bool inexact = false;
+  for (int f = 0; f < nprog; ++f) {
+    const pft_ic_prog* p = &progs[f];
+    if (p->n < 1 || !p->op || !p->arg || p->ntab < 0 || (p->ntab > 0 && (!p->tab_axis || !p->tab_off || !p->tab_val || !p->tab_err)))
+      return -2;
+    int depth = 0;
+    for (int c = 0; c < p->n; ++c) {
+      const int o = p->op[c];
+      if (o == 100)
+        ++depth;
+      else if (o == 101) {
+        if (p->arg[c] != 6.0 && p->arg[c] != 7.0 && p->arg[c] != 8.0) return -2;
+        ++depth;
+      } else if (o == 102) {
+        const double t = p->arg[c];
+        if (!(t >= 0 && t < p->ntab) || t != (double)(int)t) return -2;
+        ++depth;
+      } else if (!((o >= 1 && o <= 15) || (o >= 20 && o <= 48)))
+        return -2;
+      else {
+        if (o == 5 || o == 6 || !pft_ic_op_device(o)) inexact = true;
+        if (o < 20) --depth;
+      }
+      if (depth < 1) return -2;
+      if (depth > PFT_IC_STACK) inexact = true;
+    }
+    if (depth != 1) return -2;
+    for (int t = 0; t < p->ntab; ++t) {
+      const int ax = p->tab_axis[t];
+      const long len = (t + 1 < p->ntab ? p->tab_off[t + 1] : p->tab_len) - p->tab_off[t];
+      if (ax < 0 || ax > 2 || p->tab_off[t] < 0 || len != (ax == 0 ? s->d.n1 : (ax == 1 ? s->d.n2 : n3))) return -2;
+    }
+    entries += p->n;
+    tvals += p->ntab > 0 ? p->tab_len : 0;
+  }
+  if (entries > PFT_FORMULA_MAX_ENTRIES || tvals > 0x7fffffffL) return -2;
+  if (inexact) return 1;
+  // the blob: [arg][tval][code][meta][terr]
+  const size_t nv = (size_t)(tvals > 0 ? tvals : 1);
+  const size_t o_arg = 0, o_val = o_arg + sizeof(double) * (size_t)entries, o_code = o_val + sizeof(double) * nv,
+               o_meta = o_code + sizeof(int2) * (size_t)entries, o_err = o_meta + sizeof(int) * 3 * PFT_FORMULA_MAX,
+               blob = o_err + nv;
+  if (blob > s->formula_prog_cap) {
+    const size_t cap = 2 * blob;
+    if (s->formula_prog_dev) HIPCHK(hipFree(s->formula_prog_dev));
+    if (s->formula_prog_host) HIPCHK(hipHostFree(s->formula_prog_host));
+    s->formula_prog_dev = s->formula_prog_host = nullptr;
+    s->formula_prog_cap = 0;
+    HIPCHK(hipMalloc((void**)&s->formula_prog_dev, cap));
+    HIPCHK(hipHostMalloc((void**)&s->formula_prog_host, cap, hipHostMallocDefault));
+    s->formula_prog_cap = cap;
+  }
+  {
+    char* h = s->formula_prog_host;
+    double* h_arg = (double*)(h + o_arg);
+    double* h_val = (double*)(h + o_val);
+    int2* h_code = (int2*)(h + o_code);
+    int* h_meta = (int*)(h + o_meta);
+    unsigned char* h_err = (unsigned char*)(h + o_err);
+    long c_at = 0, v_at = 0;
+    h_val[0] = 0.0, h_err[0] = 0;
+    for (int f = 0; f < nprog; ++f) {
+      const pft_ic_prog* p = &progs[f];
+      int need = 0;
+      h_meta[3 * f] = (int)c_at;
+      for (int c = 0; c < p->n; ++c, ++c_at) {
+        const int o = p->op[c];
+        h_arg[c_at] = p->arg[c];
+        h_code[c_at] = make_int2(o, 0);
+        if (o == 101) {
+          const int q = (int)p->arg[c] - 6;
+          h_code[c_at].y = q;
+          need |= 1 << q;
+        } else if (o == 102) {
+          const int t = (int)p->arg[c], ax = p->tab_axis[t];
+          h_code[c_at] = make_int2(102 + ax, (int)(v_at + p->tab_off[t]));
+          if (ax < 2) need |= FM_NEED_IJ;
+        }
+      }
+      h_meta[3 * f + 1] = (int)c_at;
+      h_meta[3 * f + 2] = need;
+      if (p->ntab > 0) {
+        memcpy(h_val + v_at, p->tab_val, sizeof(double) * (size_t)p->tab_len);
+        memcpy(h_err + v_at, p->tab_err, (size_t)p->tab_len);
+        v_at += p->tab_len;
+      }
+    }
+  }
+  const size_t words = (size_t)FD_REC * (PFT_FORMULA_MAX + (size_t)PFT_FORMULA_MAX * n3);
+  if (!s->formula_dev) HIPCHK(hipMalloc((void**)&s->formula_dev, sizeof(unsigned long long) * words));
+  if (!s->formula_host) HIPCHK(hipHostMalloc((void**)&s->formula_host, sizeof(unsigned long long) * words, hipHostMallocDefault));
+  FormulaProgs P;
+  P.arg = (const double*)(s->formula_prog_dev + o_arg);
+  P.tval = (const double*)(s->formula_prog_dev + o_val);
+  P.code = (const int2*)(s->formula_prog_dev + o_code);
+  P.meta = (const int*)(s->formula_prog_dev + o_meta);
+  P.terr = (const unsigned char*)(s->formula_prog_dev + o_err);
+  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
+  const double* fu = s->buf[buf] + plane;
+  const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
+  // pft_slab_means' cut of the planes into work items; the cap holds per program
+  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
+  const long wg_elems = 2L * PFT_DIAG_WG_PAIRS;
+  long want = cap / n3;
+  if (want < 1) want = 1;
+  const long seg_len = ((plane + want - 1) / want + wg_elems - 1) / wg_elems * wg_elems;
+  const long segs = (plane + seg_len - 1) / seg_len;
+  const long items = segs * n3;
+  const long wgs = items < cap ? items : cap;
+  const size_t used = sizeof(unsigned long long) * FD_REC * (PFT_FORMULA_MAX + (size_t)nprog * n3);
+  HIPCHK(hipMemcpyAsync(s->formula_prog_dev, s->formula_prog_host, blob, hipMemcpyHostToDevice, s->stream));
+  // no state carries over between calls: every accumulator word is zeroed on the stream first
+  HIPCHK(hipMemsetAsync(s->formula_dev, 0, used, s->stream));
+  if (s->formula_timing) HIPCHK(hipEventRecord(s->ev_formula[0], s->stream));
+  formula_kernel<<<dim3((unsigned)wgs, (unsigned)nprog), PFT_DBLOCK, 0, s->stream>>>(
+      fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head, s->d.n1, n3, (int)segs, (int)seg_len, P, s->formula_dev);
+  HIPCHK(hipGetLastError());
+  formula_total_kernel<<<dim3((FD_REC + 63) / 64, (unsigned)nprog), 256, 0, s->stream>>>(s->formula_dev, n3);
+  HIPCHK(hipGetLastError());
+  if (s->formula_timing) HIPCHK(hipEventRecord(s->ev_formula[1], s->stream));
+  const size_t back = per_plane ? used : sizeof(unsigned long long) * FD_REC * (size_t)nprog;
+  HIPCHK(hipMemcpyAsync(s->formula_host, s->formula_dev, back, hipMemcpyDeviceToHost, s->stream));
+  const int rc = slab_wait(s, nullptr, "pft_slab_formulas");
+  if (rc) return rc;
+  for (int f = 0; f < nprog; ++f) {
+    formula_record(s->formula_host + (size_t)f * FD_REC, n, &total[f]);
+    if (per_plane)
+      for (int k = 0; k < n3; ++k)
+        formula_record(s->formula_host + (size_t)(PFT_FORMULA_MAX + (size_t)f * n3 + k) * FD_REC, plane,
+                       &per_plane[(size_t)f * n3 + k]);
+  }
+  return 0;
+}
+
+int pft_slab_formulas_timing(pft_slab* s, int on)
+{
+  if (!s) return -2;
+  for (int i = 0; i < 2 && on; ++i)
+    if (!s->ev_formula[i]) HIPCHK(hipEventCreate(&s->ev_formula[i]));
+  s->formula_timing = on ? 1 : 0;
+  return 0;
+}
+
+int pft_slab_formulas_last_ms(pft_slab* s, double* ms)
+{
+  if (!s || !ms || !s->formula_timing) return -2;
+  float f = 0.0f;
+  HIPCHK(hipEventElapsedTime(&f, s->ev_formula[0], s->ev_formula[1]));
   *ms = f;
   return 0;
 }

@@ -4,7 +4,7 @@
 // kernels' template arguments.  The translation units over the C ABI of include/pft_hip.h:
 //   pft_kernels.hip  the step kernels (merson_stage, merson_fused, merson_pair), the slab object's
 //                    API, the pft_hip_* shim, the halo exchange, IC
-//   pft_reduce.hip   diagnostics and exact means (f5, f6)
+//   pft_reduce.hip   diagnostics, exact means and formula diagnostics (f5, f6, f12)
 //   pft_snap.hip     snapshots (f7), region snapshots (f11)
 // No device code crosses files: nothing is device-linked.  Every .hip includes this header first.
 #pragma once
@@ -199,6 +199,17 @@ struct pft_slab {
   unsigned long long* means_host;    // pinned
   int means_timing;
   hipEvent_t ev_means[2];
+  // f12 formula diagnostics (pft_slab_formulas): PFT_FORMULA_MAX total records, then n3 plane
+  // records per program, and their pinned host copy, allocated by the first call; the programs
+  // and their tables as one blob (device and pinned host, grown on demand); events around the
+  // kernel pair
+  unsigned long long* formula_dev;
+  unsigned long long* formula_host;  // pinned
+  char* formula_prog_dev;
+  char* formula_prog_host;           // pinned
+  size_t formula_prog_cap;
+  int formula_timing;
+  hipEvent_t ev_formula[2];
   // f7 snapshots (pft_slab_snapshot_export / pft_slab_image): the image-sized pinned, host-mapped
   // buffer the background writer reads (allocated by the first call, freed at destroy once the
   // writer is done with it), the device staging image of the staged host link, events around the

@@ -20,8 +20,10 @@
  */
 #include "pft_internal.h"
 #include "../../include/pft_frontend.h"
+#include "../../include/pft_formula.h"
 
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -804,6 +806,98 @@ int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means *
 	*global = all[0].m;
 	for(r = 1; r < nprocs; r++) pft_means_combine(global, &all[r].m);
 	if(local) *local = mine.m;
+	free(all);
+	return 0;
+}
+
+int pft_solver_formulas(int nprog, const int * lens, const int * ops, const double * args, pft_fdiag * global,
+                        pft_fdiag * local, pft_fdiag * per_plane)
+{
+	/* f12: the formula diagnostics of the device-resident x, under pft_solver_diag's rules.  Every
+	   rank compiles first and the outcome is agreed before any device work, as in
+	   pft_solver_ic_formulas_device: 1 (not device-exact) and -2 (a bad program) are the same on every
+	   rank, -1 (out of memory) is local -- every rank returns the same code, -1 over -2 over 1.  Then
+	   each rank reduces its slab and the records travel with its status in rounds of at most 256
+	   bytes, as pft_solver_means' do; they are merged in rank order */
+	enum { ROUND = 256 };
+	struct formula_msg { long long status; pft_fdiag d[PFT_FORMULA_MAX]; };
+	struct formula_msg * all;    /* (loopback ranks are threads of one process: nothing static) */
+	char piece[PFT_DIAG_MAX_RANKS * ROUND];
+	struct formula_msg mine;
+	pft_ic_prog pr[PFT_FORMULA_MAX];
+	pft_grid g;
+	pft_comm * c = comm();
+	const int nprocs = pft_comm_size(c);
+	int rc = 0, r, f, off = 0, entries = 0, bad = 0, first_bad = 0;
+	size_t at, used;
+	if(!global) return -2;
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if(R.in_callback && nprocs > 1) return -2;
+	if(nprocs > PFT_DIAG_MAX_RANKS) return -2;
+	if(nprog < 1 || nprog > PFT_FORMULA_MAX || !lens || !ops || !args || pft_model_get_grid(&g)) rc = -2;
+	for(f = 0; f < nprog && !rc; f++) {
+		if(lens[f] < 1 || (entries += lens[f]) > PFT_FORMULA_MAX_ENTRIES) rc = -2;
+	}
+	memset(pr, 0, sizeof pr);
+	for(f = 0; f < nprog && !rc; f++) {
+		rc = pft_formula_compile(&g, lens[f], ops + off, args + off, &pr[f]);
+		off += lens[f];
+	}
+	if(nprocs > 1) {
+		long long v = rc == -1 ? 3 : (rc == -2 ? 2 : (rc == 1 ? 1 : (rc ? 3 : 0)));
+		int crc = pft_comm_allreduce_max_i64(c, &v);
+		if(crc) {
+			for(f = 0; f < PFT_FORMULA_MAX; f++) pft_ic_prog_free(&pr[f]);
+			R.last_status = crc;
+			return PFT_SOLVE_DEVICE_ERROR;
+		}
+		rc = v == 3 ? -1 : (v == 2 ? -2 : (v == 1 ? 1 : 0));
+	}
+	if(rc) {
+		for(f = 0; f < PFT_FORMULA_MAX; f++) pft_ic_prog_free(&pr[f]);
+		return rc;
+	}
+	memset(&mine, 0, sizeof mine);
+	rc = pft_slab_formulas(R.slab, PFT_BUF_X, nprog, pr, mine.d, per_plane);
+	for(f = 0; f < PFT_FORMULA_MAX; f++) pft_ic_prog_free(&pr[f]);
+	mine.status = rc;
+	if(nprocs == 1) {
+		if(rc) { R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
+		for(f = 0; f < nprog; f++) {
+			global[f] = mine.d[f];
+			if(local) local[f] = mine.d[f];
+		}
+		return 0;
+	}
+	used = offsetof(struct formula_msg, d) + (size_t)nprog * sizeof(pft_fdiag);
+	/* (a failed allocation is this rank's failure, met after the rounds like any other) */
+	all = (struct formula_msg *)malloc((size_t)nprocs * sizeof *all);
+	if(!all && !mine.status) mine.status = -1;
+	for(at = 0; at < used; at += ROUND) {
+		const int bytes = (int)(used - at < ROUND ? used - at : ROUND);
+		if((rc = pft_comm_allgather(c, (const char *)&mine + at, bytes, piece))) {
+			free(all);
+			R.last_status = rc;
+			return PFT_SOLVE_DEVICE_ERROR;
+		}
+		if(at == 0)
+			for(r = 0; r < nprocs; r++) {
+				long long st;
+				memcpy(&st, piece + (size_t)r*bytes, sizeof st);
+				if(st) { bad = 1; if(!first_bad) first_bad = (int)st; }
+			}
+		for(r = 0; r < nprocs && all; r++) memcpy((char *)&all[r] + at, piece + (size_t)r*bytes, bytes);
+	}
+	if(bad) {
+		free(all);
+		R.last_status = mine.status ? (int)mine.status : first_bad;
+		return PFT_SOLVE_DEVICE_ERROR;
+	}
+	for(f = 0; f < nprog; f++) {
+		global[f] = all[0].d[f];
+		for(r = 1; r < nprocs; r++) pft_fdiag_combine(&global[f], &all[r].d[f]);
+		if(local) local[f] = mine.d[f];
+	}
 	free(all);
 	return 0;
 }

@@ -128,7 +128,7 @@ _OPS = [
     ("acosh", UNARY, 16, _dom(lambda x: x >= 1, _ovf(lambda x: math.log(x + math.sqrt(math.pow(x, 2) - 1)))), 37),
     ("atanh", UNARY, 16, _dom(lambda x: abs(x) < 1, lambda x: math.log((1 + x) / (1 - x)) / 2), 38),
     ("log", UNARY, 16, _dom(lambda x: x > 0, math.log10), 39), ("ln", UNARY, 16, _dom(lambda x: x > 0, math.log), 40),
-    ("sqrt", UNARY, 16, _dom(lambda x: x >= 0, math.sqrt), 41), ("exp", UNARY, 16, _ovf(math.exp), 42),
+    ("sqrt", UNARY, 16, _dom(lambda x: not x < 0, math.sqrt), 41), ("exp", UNARY, 16, _ovf(math.exp), 42),
     ("pow10", UNARY, 16, _dom(lambda x: x <= 308, lambda x: math.pow(10, x)), 43),
     ("^", BINARY, 14, _power, 7), ("root", BINARY, 14, lambda x, y: _power(y, 1 / x) if x != 0 else _power(0, -1), 8),
     ("!", POSTFIX, 12, _fact, 44),
@@ -317,17 +317,21 @@ class Evaluator:
         return out
 
     # -- evaluation (exp_all.cc:229-256, 779-859), optionally emitting the postfix program ----
-    def run(self, tokens, emit=None, symbolic=()):
+    def run(self, tokens, emit=None, symbolic=(), evaluate=True):
         """evaluate parsed tokens; `emit` (a list) receives the postfix program; variables named
-        in `symbolic` are program inputs (their current value is used for the evaluation)"""
+        in `symbolic` are program inputs (their current value is used for the evaluation).
+        evaluate=False only emits: no operator is applied (the inputs' current values cannot raise
+        a math error) and the value returned means nothing"""
         vst, ost = [], []
 
         def apply(op):
             if op[0] == UNARY:
-                vst[-1] = op[1][3](vst[-1])
+                if evaluate:
+                    vst[-1] = op[1][3](vst[-1])
             else:
                 y = vst.pop()
-                vst[-1] = op[1][3](vst[-1], y)
+                if evaluate:
+                    vst[-1] = op[1][3](vst[-1], y)
             if emit is not None:
                 emit.append((op[1][4], 0.0))
 
@@ -350,7 +354,8 @@ class Evaluator:
                 ost.append((BINARY, x))
             elif kind == POSTFIX:
                 reduce(-x[2] if x[2] < 0 else x[2])
-                vst[-1] = x[3](vst[-1])
+                if evaluate:
+                    vst[-1] = x[3](vst[-1])
                 if emit is not None:
                     emit.append((x[4], 0.0))
             elif kind == UNARY:
@@ -374,11 +379,13 @@ class Evaluator:
     def eval(self, expr):
         return self.run(self.parse(expr))
 
-    def compile(self, expr, inputs):
+    def compile(self, expr, inputs, evaluate=True):
         """postfix program of `expr` with `inputs` as per-node variables (their values must be
-        defined, any value); constants folded to their current values"""
+        defined, any value); constants folded to their current values.  evaluate=False: the
+        program alone, without evaluating it on the inputs' current values (f12: a formula may
+        well have a math error there)"""
         prog = []
-        self.run(self.parse(expr), emit=prog, symbolic=tuple(inputs))
+        self.run(self.parse(expr), emit=prog, symbolic=tuple(inputs), evaluate=evaluate)
         return prog
 
 
@@ -514,7 +521,7 @@ class Case:
 
     def run(self, nprocs=1, rank=0, beads=None, snapshot_path=None, comment="", diag=True, opts=None,
             means=False, snapshot_where="host", snapshot_async=False, regions=None, region_every=1,
-            snapshot_full=True, **kw):
+            snapshot_full=True, formulas=None, **kw):
         """the whole case as the driver runs it (intertrack.c:2265-2283): this slab's simulation
         (simulation(); **kw goes to it), then saved_files snapshots up to final_time
         (Simulation.run_series; means=True: every row also carries the exact means).  Returns the
@@ -527,8 +534,14 @@ class Case:
         regions / region_every / snapshot_full: run_series' region datasets (f11), given here in
         Python.  The parameter file's slice_output, slice_along and slice_reverse_order stay the
         no-ops they are in the reference driver, which parses and skips them (they belong to its
-        slicing tool): no Params word selects a region."""
+        slicing tool): no Params word selects a region.
+        formulas={name: expression} (f12): run_series' formula diagnostics, evaluated with this case's
+        own evaluator, so every variable of the parameter file (u_star, L3, water_cp, ...) can appear;
+        given here in Python -- the reference driver has no Params word for them either."""
         final_time, saved_files, first, skip_first = self.final_time, self.saved_files, 0, False
+        if formulas is not None:
+            from . import formula_programs
+            formulas = formula_programs(formulas, self.ev)     # an undefined symbol ends the run before any work
         if self.continue_series and not self.icond_mode:
             warnings.warn("continue_series is only meaningful when the initial conditions are loaded from file")
         elif self.continue_series:
@@ -540,7 +553,8 @@ class Case:
             return sim.run_series(final_time, saved_files, snapshot_path=snapshot_path, comment=comment,
                                   diag=diag, opts=opts, means=means, snapshot_where=snapshot_where,
                                   snapshot_async=snapshot_async, first_snapshot=first, skip_first=skip_first,
-                                  regions=regions, region_every=region_every, snapshot_full=snapshot_full)
+                                  regions=regions, region_every=region_every, snapshot_full=snapshot_full,
+                                  formulas=formulas)
         finally:
             sim.close()
 
