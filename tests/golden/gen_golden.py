@@ -42,6 +42,11 @@ Cases (SURVEY.md section 4.2 KATs 1-4):
   gthaw    g20 with phase_switch_time 100 s: the trajectory record for calc_mode 0, 1 and 2 to
            t = 36, 360 and 720 s across the freeze-to-thaw switch of the top temperature
            (equation.c:96-111), checked identical on 3 ranks.
+  gedge    L1=0.22, L2=0.12, L3=0.03, grid_nodes 44 -> 44x24x6, the dense edge-value state of
+  gedgep   tests/_dense.py (clamped p and gl, p on the sshape thresholds, u on u_star): the RHS of every
+           calc_mode and the first six attempted steps from h = 1 s; gedge with the default constants,
+           gedgep with every physical constant perturbed through the Params text (trajectories of
+           calc_mode 0 and 1 only); each checked identical on 3 ranks.
 
     python tests/golden/gen_golden.py [case ...]     (default: all)
 """
@@ -550,11 +555,97 @@ def case_ragged():
     return arrays, meta
 
 
+# 44 x 24 x 6 cells of 5 mm: xi = L3/100 is 0.3 mm, and from h = 1 s the step control rejects two to
+# four of the first six attempts instead of one (at 1 mm cells the first attempt overflows and the
+# accepted steps that follow are picoseconds long, too short to move the state's upper bits)
+GEDGE_GRID = {"L1": 0.22, "L2": 0.12, "L3": 0.03, "grid_nodes": 44}
+GEDGE_T = 100.0
+GEDGE_ATTEMPTS = 6
+
+
+def gedge_replacements(perturbed):
+    """the Params lines of the gedge grid; perturbed: every physical constant's own expression times
+    its factor of tests/_dense.py (alpha, water_rho*water_cp in Params, follows from its formula)"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _dense as D
+    rep = dict(GEDGE_GRID)
+    if perturbed:
+        src = open(os.path.join(REF_APP, "Params")).read()
+        for k, f in D.factors().items():
+            if k == "alpha":
+                continue
+            m = re.search(r"^" + re.escape(k) + r"[ \t]+(.*)$", src, re.M)
+            rep[k] = f"({m.group(1).strip()})*{f!r}"
+        for k, v in D.FIXED.items():
+            rep[k] = repr(v)
+    return rep
+
+
+def case_gedge(perturbed=False):
+    """a dense edge-value state (tests/_dense.py: every cell differs from its neighbours; p below 0,
+    above 1 and on sshape's thresholds, gl on 1/zeta, u on u_star) on a grid of several pair
+    tiles and fused16 tiles a plane: the RHS of every calc_mode at one time, and the reference's
+    first six attempted steps from h = 1 (solvex, interrupted by its callback at the accepted step
+    that is the sixth attempt), each checked identical on 3 ranks (two planes a rank).  gedge: the
+    default constants, every mode; gedgep: perturbed constants, trajectories of modes 0 and 1.
+    A component that a run leaves as it was (gl always; u in modes 10 and 11) is not stored."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _dense as D
+    name = "gedgep" if perturbed else "gedge"
+    rep = gedge_replacements(perturbed)
+    arrays, meta = {}, {"case": name, "source": "reference Params, " + ", ".join(f"{k}={v}" for k, v in rep.items()),
+                        "state_seed": D.SEED, "rhs_time": GEDGE_T, "attempts": GEDGE_ATTEMPTS}
+    st = None
+    for mode in (0, 1, 2, 10, 11):
+        w = Work(dict(rep, calc_mode=mode))
+        try:
+            p = read_params(w.run(1, "setup"))
+            n1, n2, n3 = p["n1"], p["n2"], p["n3"]
+            assert n1 % 2 == 0 and n1 > 40 and n3 >= 5, (n1, n2, n3)
+            shape = (3, n3, n2, n1)
+            if st is None:
+                meta["params"] = hexify(p)
+                st = D.edge_state(n1, n2, n3, np.array([p[k] for k in D.PARAM_NAMES]), D.SEED)
+                arrays["state"] = st
+            meta[f"m{mode}_params"] = hexify(p)
+            sp = os.path.join(w.dir, "state.f64")
+            st.tofile(sp)
+            o1, o3 = w.run(1, "rhs", sp, GEDGE_T), w.run(3, "rhs", sp, GEDGE_T)
+            K = load(os.path.join(o1, "rhs.f64"), shape)
+            assert np.array_equal(K, load(os.path.join(o3, "rhs.f64"), shape)), f"rhs decomposition mismatch mode {mode}"
+            assert np.isfinite(K).all() and not K[2].any()
+            arrays[f"rhs_m{mode}"] = K[:2]                       # dgl is 0 everywhere
+            if perturbed and mode not in (0, 1):
+                continue
+            for brk in range(1, GEDGE_ATTEMPTS + 1):             # stop at the brk-th accepted step
+                tm, _, xs = traj_ext(w.run(1, "solvex", sp, 0.0, 1.0, 0, brk, 1e9), 1, shape)
+                if tm[0][3] >= GEDGE_ATTEMPTS:
+                    break
+            tm3, _, xs3 = traj_ext(w.run(3, "solvex", sp, 0.0, 1.0, 0, brk, 1e9), 1, shape)
+            assert tm == tm3 and np.array_equal(xs[0], xs3[0]), f"decomposition invariance broken for mode {mode}"
+            t, h, steps, total, rc, nan = tm[0]
+            assert total == GEDGE_ATTEMPTS and rc == 1 and nan == 0, f"mode {mode}: {tm[0]} -- change the seed"
+            assert steps >= 2 and total - steps >= 1 and np.isfinite(xs[0]).all(), f"mode {mode}: {tm[0]} -- change the seed"
+            meta[f"traj_m{mode}"] = tm[0][:4]
+            for q in range(3):
+                if not np.array_equal(xs[0][q], st[q]):
+                    arrays[f"traj_m{mode}_q{q}"] = xs[0][q]
+            assert f"traj_m{mode}_q2" not in arrays and f"traj_m{mode}_q1" in arrays
+        finally:
+            w.close()
+    return arrays, meta
+
+
+def case_gedgep():
+    return case_gedge(perturbed=True)
+
+
 def main():
     if not os.path.exists(PFT_REF):
         sys.exit("build the reference harness first: make -C oracle ref")
     cases = {"g20": case_g20, "ragged": case_ragged, "g100": case_g100, "ctl": case_ctl, "g200": case_g200,
-             "g400": case_g400, "g20nf": case_g20nf, "gnoise": case_gnoise, "epsctl": case_epsctl, "gthaw": case_gthaw}
+             "g400": case_g400, "g20nf": case_g20nf, "gnoise": case_gnoise, "epsctl": case_epsctl, "gthaw": case_gthaw,
+             "gedge": case_gedge, "gedgep": case_gedgep}
     for name in sys.argv[1:] or list(cases):
         arrays, meta = cases[name]()
         name = meta["case"]

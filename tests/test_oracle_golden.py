@@ -5,6 +5,7 @@ Golden vectors come from the reference compiled in place (tests/golden/gen_golde
 import numpy as np
 import pytest
 
+import _dense as D
 import _oracle as O
 
 
@@ -174,3 +175,92 @@ def test_noise_trajectory_equals_reference(mode):
         assert (t.hex(), h.hex(), s, st, rc) == (float.fromhex(ref[0]).hex(), float.fromhex(ref[1]).hex(),
                                                  ref[2], ref[3], ref[4])
         assert np.array_equal(x, A[f"traj_m{mode}_state{i}"])
+
+
+# ---- dense edge-value states (tests/_dense.py; tests/golden/gedge and gedgep) --------------------
+# The oracle is pinned on the clamp and threshold branches and on foreign constants before the
+# device is compared with it (tests/test_dense_gpu.py), and the inputs of those comparisons are
+# shown to be what they are meant to be: dense, and on every branch.
+
+GEDGE = [("gedge", m) for m in D.MODES] + [("gedgep", m) for m in D.MODES]
+GEDGE_TRAJ = [("gedge", m) for m in D.MODES] + [("gedgep", 0), ("gedgep", 1)]
+DENSE_INPUTS = [("gedge", None), ("gedgep", None)] + [(d, pert) for d in D.GRIDS for pert in (False, True)]
+
+
+def _dense_input(case, perturbed):
+    if perturbed is None:
+        meta, A, Pm, info = D.golden(case)
+        return info, Pm, A["state"]
+    return D.grid_case(case, perturbed)
+
+
+def test_gedge_is_the_generator_state():
+    """the golden's state is edge_state() of the reference's own parameter values, and the perturbed
+    set differs from the default one in every physical constant"""
+    for name in ("gedge", "gedgep"):
+        meta, A, Pm, info = D.golden(name)
+        assert (info["n1"], info["n2"], info["n3"]) == (44, 24, 6)
+        assert np.array_equal(A["state"], D.edge_state(44, 24, 6, Pm, meta["state_seed"]))
+    P0, Pp = D.golden("gedge")[2], D.golden("gedgep")[2]
+    for k in D.PHYSICAL + list(D.FIXED):
+        assert P0[D.PARAM_NAMES.index(k)] != Pp[D.PARAM_NAMES.index(k)], k
+    for k, v in D.FIXED.items():
+        assert Pp[D.PARAM_NAMES.index(k)] == O.lib().pft_or_float_val(repr(v).encode())
+
+
+@pytest.mark.parametrize("case,mode", GEDGE)
+@pytest.mark.parametrize("nprocs", [1, 3])
+def test_rhs_gedge_bitwise(case, mode, nprocs):
+    meta, A, Pm, info = D.golden(case)
+    K, _ = O.rhs(info, Pm, mode, meta["rhs_time"], np.array(A["state"]), nprocs)
+    assert np.array_equal(K, D.golden_rhs(A, mode))
+
+
+@pytest.mark.parametrize("case,mode", GEDGE_TRAJ)
+def test_six_steps_gedge_bitwise(case, mode):
+    """the reference's first six attempted steps from h = 1 s: at least one rejected, two accepted"""
+    meta, A, Pm, info = D.golden(case)
+    t, h, steps, total, rc, x = O.solve(info, Pm, mode, np.array(A["state"]), 0.0, 1.0, [1e9],
+                                        max_steps_total=meta["attempts"])[0]
+    assert (t.hex(), h.hex(), steps, total, rc) == D.golden_record(meta, mode) + (2,)
+    assert np.array_equal(x, D.golden_final(A, mode))
+    assert total == D.ATTEMPTS and steps >= 2 and total - steps >= 1 and np.isfinite(x).all()
+
+
+@pytest.mark.parametrize("case,perturbed", DENSE_INPUTS)
+def test_dense_state_has_no_trivial_cell(case, perturbed):
+    """K_u != 0 at every cell in modes 0, 1 and 2; K_p != 0 at >= 99% of the cells with
+    1 - zeta gl > 0 in modes 0, 1, 10 and 11 (elsewhere the factor fmax(0, 1 - zeta gl) makes it 0)"""
+    info, Pm, x = _dense_input(case, perturbed)
+    wet = 1.0 - Pm[O.PARAM_NAMES.index("zeta")] * x[2] > 0
+    for mode in D.MODES:
+        K, _ = O.rhs(info, Pm, mode, 100.0, np.array(x))
+        assert np.isfinite(K).all()
+        if mode in (0, 1, 2):
+            assert np.count_nonzero(K[0]) == K[0].size, mode
+        if mode in (0, 1, 10, 11):
+            assert np.count_nonzero(K[1][wet]) >= 0.99 * wet.sum(), mode
+            assert not K[1][~wet].any()
+
+
+@pytest.mark.parametrize("case,perturbed", DENSE_INPUTS)
+def test_dense_state_populates_every_branch(case, perturbed):
+    """more than 1% of the cells on each branch of the arithmetic: p < 0 and p > 1 (fmax(p(1-p), 0)
+    clamps), the three pieces of sshape for p and for 1 - p, both sides of fmax(0, 1 - zeta gl),
+    u = u_star; and the threshold values themselves are there"""
+    info, Pm, x = _dense_input(case, perturbed)
+    for k, v in D.branch_fractions(x, Pm).items():
+        assert v > 0.01, (k, v)
+    for v in D.p_specials(Pm):
+        assert (x[1] == v).sum() > 0, v
+    for v in D.gl_specials(Pm):
+        assert (x[2] == v).sum() > 0, v
+
+
+@pytest.mark.parametrize("dims", D.GRIDS)
+@pytest.mark.parametrize("perturbed", [False, True])
+def test_dense_grids_six_steps_are_finite(dims, perturbed):
+    """the oracle's six attempted steps from h = 1 s on the larger grids: finite, steps of both kinds"""
+    for mode in D.MODES:
+        (t, h, steps, total), x = D.oracle_steps(dims, perturbed, mode)
+        assert total == D.ATTEMPTS and 1 <= steps < total and np.isfinite(x).all(), (mode, steps)
