@@ -12,6 +12,7 @@
 #include "RK_MPI_SAsolver.h"
 #include "pft_hip.h"
 #include "pft_formula.h"
+#include "pft_hist.h"
 #include "pft_io.h"
 
 #ifdef __cplusplus
@@ -74,6 +75,27 @@ int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means *
    returns the same code. */
 int pft_solver_formulas(int nprog, const int * lens, const int * ops, const double * args, pft_fdiag * global,
                         pft_fdiag * local, pft_fdiag * per_plane);
+
+/* f13: the histogram (pft_hist.h) of a formula's values over the cells a mask formula selects, of the
+   device-resident x, under the rules of pft_solver_diag word for word: valid after any fused solve
+   or device IC, -3 without an initialised solver or a resident state (never stale numbers), 0 from
+   a Service_Callback on one rank and -2 there with several.  The value: nv entries in vops / vargs
+   (pft_frontend.h); the mask: nm entries in mops / margs, or 0, NULL, NULL for none; nbins + 1
+   edges (pft_hist_check).  Every rank checks and compiles first (pft_formula_compile) and the ranks
+   agree the outcome before any device work: 1 when a program is not device-exact (nothing is
+   launched: use pft_hist_host), -2 for a bad program, bad edges or limits exceeded, the same on
+   every rank.  That first pft_comm_allgather round also carries a 64-bit hash of nbins, the edges
+   and both programs: ranks that were given different histograms all return -2, before any device
+   work.  global / global_counts[nbins]: the record of the whole grid, the same bits on every rank;
+   local / local_counts (optional): this slab's; plane_heads (optional, n3 heads) and plane_counts
+   (optional, n3 * nbins): this slab's planes'.  Collective on several ranks: each rank counts its
+   slab (pft_slab_hist) and its record travels with its status in pft_comm_allgather rounds of at
+   most 256 bytes (33 for 1024 bins); the records are merged in rank order and every rank returns
+   the same code. */
+int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, const int * mops, const double * margs,
+                    int nbins, const double * edges, pft_hist_head * global, long long * global_counts,
+                    pft_hist_head * local, long long * local_counts, pft_hist_head * plane_heads,
+                    long long * plane_counts);
 
 /* f1 (after RK_MPI_SA_init): the default Params' initial condition (Params:9-21,
    intertrack.c:1880-2010) and, with with_beads, the glass beads (PrecalculateData,

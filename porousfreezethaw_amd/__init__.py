@@ -243,6 +243,105 @@ def formula_programs(formulas, variables=None):
     return names, lens, ops, args
 
 
+PFT_HIST_MAX_BINS = 1024                               # include/pft_hist.h
+HIST_ROW_KEYS = ("under", "over", "nan", "selected")   # run_series: <name> (the counts) and <name>_<key>
+
+
+class pft_hist_head(C.Structure):
+    """include/pft_hist.h: the head of a histogram record; selected == nan + under + over + sum(counts)"""
+    _fields_ = [("cells", C.c_longlong), ("selected", C.c_longlong), ("nan", C.c_longlong),
+                ("under", C.c_longlong), ("over", C.c_longlong)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class pft_hist_prog(C.Structure):
+    """include/pft_hist.h: a formula as pft_hist_host takes it"""
+    _fields_ = [("n", C.c_int), ("op", C.POINTER(C.c_int)), ("arg", C.POINTER(C.c_double))]
+
+
+def hist_edges(bins, range=None):
+    """The edge array of a histogram (f13), float64 [nbins + 1] -- the contract of every histogram
+    entry, which returns it too.  An int `bins` with range=(lo, hi): np.linspace(lo, hi, bins + 1);
+    an array is taken as the edges (range must then be None).  ValueError for everything
+    pft_hist_check refuses: fewer than 1 or more than PFT_HIST_MAX_BINS bins, an edge that is NaN
+    or +-Inf, edges that are not strictly increasing (equal neighbours, -0.0 next to +0.0)."""
+    if isinstance(bins, (int, np.integer)) and not isinstance(bins, bool):
+        if range is None:
+            raise ValueError("hist_edges: an int `bins` needs range=(lo, hi)")
+        if not 1 <= int(bins) <= PFT_HIST_MAX_BINS:
+            raise ValueError(f"hist_edges: bins must be in 1..{PFT_HIST_MAX_BINS}, not {bins}")
+        try:
+            lo, hi = (float(v) for v in range)
+        except (TypeError, ValueError):
+            raise ValueError(f"hist_edges: range must be (lo, hi), not {range!r}") from None
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError(f"hist_edges: range must be finite with lo < hi, not {range!r}")
+        edges = np.linspace(lo, hi, int(bins) + 1)
+    else:
+        if range is not None:
+            raise ValueError("hist_edges: range= goes with an int `bins`, not with an edge array")
+        try:
+            edges = np.ascontiguousarray(bins, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"hist_edges: bins must be an int or an array of edges, not {bins!r}") from None
+        if edges.ndim != 1 or not 2 <= edges.size <= PFT_HIST_MAX_BINS + 1:
+            raise ValueError(f"hist_edges: 2..{PFT_HIST_MAX_BINS + 1} edges in one dimension, not shape {edges.shape}")
+        edges = edges.copy()
+    if lib().pft_hist_check(edges.size - 1, _dp(edges)):
+        raise ValueError("hist_edges: the edges must be finite and strictly increasing")
+    return edges
+
+
+def hist_spec(formula, bins, range=None, mask=None, variables=None):
+    """A histogram compiled for Simulation.histogram / run_series: the edges (hist_edges) and the
+    postfix programs of the value formula and of the optional mask formula (formula_programs; its
+    `variables`).  ValueError before any work for bad edges, an undefined symbol or a syntax error."""
+    edges = hist_edges(bins, range)
+    value = formula_programs({"formula": formula}, variables)
+    masked = None if mask is None else formula_programs({"mask": mask}, variables)
+    if masked is not None and len(value[2]) + len(masked[2]) > PFT_FORMULA_MAX_ENTRIES:
+        raise ValueError(f"histogram: formula and mask together have more than {PFT_FORMULA_MAX_ENTRIES} entries")
+    return {"compiled": True, "formula": str(formula), "mask": None if mask is None else str(mask), "edges": edges,
+            "value": value, "masked": masked}
+
+
+def hist_quantile(h, q):
+    """The bracket (lo, hi) of the bin that holds the q-quantile (0 <= q <= 1) of the selected values
+    that are not NaN, of a histogram dict `h` (edges, counts, under, over): the first bin, in the
+    order under, the bins, over, at which the cumulated count reaches ceil(q * N), at least 1.
+    (-inf, edges[0]) or (edges[-1], inf) when it falls in under or over.  Integer arithmetic only:
+    q enters as the exact ratio of the double.  ValueError for a q outside [0, 1] or when N is 0."""
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"hist_quantile: q must be in [0, 1], not {q!r}")
+    edges = h["edges"]
+    counts = [int(c) for c in h["counts"]]
+    under, over = int(h["under"]), int(h["over"])
+    total = under + sum(counts) + over
+    if total == 0:
+        raise ValueError("hist_quantile: no selected value that is not NaN")
+    num, den = q.as_integer_ratio()
+    target = max(1, -(-num * total // den))
+    cum = under
+    if cum >= target:
+        return (float("-inf"), float(edges[0]))
+    for b, c in enumerate(counts):
+        cum += c
+        if cum >= target:
+            return (float(edges[b]), float(edges[b + 1]))
+    return (float(edges[-1]), float("inf"))
+
+
+def write_hist_txt(rows, path, key):
+    """one line per snapshot: the counts of histogram `key` (run_series(histograms=)'s rows) as
+    decimal integers separated by blanks"""
+    with open(path, "w") as f:
+        for r in rows:
+            f.write(" ".join(str(int(c)) for c in r[key]) + "\n")
+
+
 class pft_ic_prog(C.Structure):
     """include/pft_frontend.h: a program compiled for the device (owned by the library: pft_ic_prog_free)"""
     _fields_ = [("n", C.c_int), ("op", C.POINTER(C.c_int)), ("arg", C.POINTER(C.c_double)), ("ntab", C.c_int),
@@ -360,6 +459,15 @@ def lib():
         L.pft_slab_formulas_timing.argtypes = [C.c_void_p, C.c_int]
         L.pft_slab_formulas_last_ms.argtypes = [C.c_void_p, dp]
         L.pft_solver_formulas.argtypes = [C.c_int, ip, ip, dp, fp, fp, fp]
+        hp, hpp, llp = C.POINTER(pft_hist_head), C.POINTER(pft_hist_prog), C.POINTER(C.c_longlong)
+        L.pft_hist_check.argtypes = [C.c_int, dp]
+        L.pft_hist_bin.argtypes = [C.c_int, dp, C.c_double]
+        L.pft_hist_combine.argtypes = [C.c_int, hp, llp, hp, llp]
+        L.pft_hist_host.argtypes = [gp, dp, hpp, hpp, C.c_int, dp, hp, llp, hp, llp]
+        L.pft_slab_hist.argtypes = [C.c_void_p, C.c_int, icp, icp, C.c_int, dp, hp, llp, hp, llp]
+        L.pft_slab_hist_timing.argtypes = [C.c_void_p, C.c_int]
+        L.pft_slab_hist_last_ms.argtypes = [C.c_void_p, dp]
+        L.pft_solver_hist.argtypes = [C.c_int, ip, dp, C.c_int, ip, dp, C.c_int, dp, hp, llp, hp, llp, hp, llp]
         rp, vpp = C.POINTER(pft_snapshot_ranges), C.POINTER(C.c_void_p)
         L.pft_snapshot_image_bytes.argtypes = [gp]
         L.pft_snapshot_image_bytes.restype = C.c_size_t
@@ -920,6 +1028,122 @@ class Simulation:
             out[name] = d
         return out
 
+    # -- f13: histograms of formula values -----------------------------------------------------------
+    def _hist_host_global(self, spec, plane_heads, plane_counts):
+        """pft_hist_host of self.x, merged over the communicator's ranks in rank order (collective;
+        the record travels in pft_comm_allgather rounds of at most 256 bytes)"""
+        L_ = self.lib
+        edges = spec["edges"]
+        nbins = edges.size - 1
+        _, _, vops, vargs = spec["value"]
+        value = pft_hist_prog(len(vops), _ip(vops), _dp(vargs))
+        mask = None
+        if spec["masked"] is not None:
+            _, _, mops, margs = spec["masked"]
+            mask = C.byref(pft_hist_prog(len(mops), _ip(mops), _dp(margs)))
+        head, counts = pft_hist_head(), (C.c_longlong * nbins)()
+        rc = L_.pft_hist_host(C.byref(self.grid), _dp(self.x), C.byref(value), mask, nbins, _dp(edges), C.byref(head),
+                              counts, plane_heads, plane_counts)
+        if rc:
+            raise RuntimeError(f"pft_hist_host failed ({rc})")
+        comm = L_.pft_comm_current()
+        n = L_.pft_comm_size(comm) if comm else 1
+        if n == 1:
+            return (head, counts), (head, counts)
+        raw = bytes(head) + bytes(counts)
+        parts = [bytearray() for _ in range(n)]
+        for off in range(0, len(raw), 256):
+            piece = raw[off:off + 256]
+            every = C.create_string_buffer(n * len(piece))
+            rc = L_.pft_comm_allgather(comm, piece, len(piece), every)
+            if rc:
+                raise RuntimeError(f"pft_comm_allgather failed ({rc})")
+            for r in range(n):
+                parts[r] += every.raw[r * len(piece):(r + 1) * len(piece)]
+        hs = C.sizeof(pft_hist_head)
+        ghead = pft_hist_head.from_buffer_copy(bytes(parts[0][:hs]))
+        gcounts = (C.c_longlong * nbins).from_buffer_copy(bytes(parts[0][hs:]))
+        for r in range(1, n):
+            oh = pft_hist_head.from_buffer_copy(bytes(parts[r][:hs]))
+            oc = (C.c_longlong * nbins).from_buffer_copy(bytes(parts[r][hs:]))
+            L_.pft_hist_combine(nbins, C.byref(ghead), gcounts, C.byref(oh), oc)
+        return (ghead, gcounts), (head, counts)
+
+    def histogram(self, formula, bins, range=None, mask=None, variables=None, where="device", per_plane=False):
+        """f13: the histogram of a formula of the parameter file's language (see formulas()) over the
+        interior cells of the whole grid that the formula `mask` selects (value != 0, so a NaN
+        selects; a math error does not; None: every cell) -- numpy.histogram(values[selected],
+        bins=edges) with the NaN left out, by integer counts (include/pft_hist.h).  bins / range: see
+        hist_edges().  Returns a dict: edges, counts (int64 [nbins]), under, over, nan, selected and
+        cells, with selected == nan + under + over + counts.sum() -- the same numbers on any
+        decomposition.  where="device": of the device-resident state, by pft_solver_hist -- no
+        download; collective on several ranks; RuntimeError when nothing is resident; ValueError
+        naming the formula when the formula or the mask is not device-exact (use where="host").
+        where="host": pft_hist_host of self.x, merged over the ranks (collective too); it accepts
+        every formula.  per_plane: also counts_per_plane (int64 [n3_local, nbins]), under_per_plane,
+        over_per_plane, nan_per_plane, selected_per_plane (this rank's planes, global rows first_row
+        + k), first_row and "local", this slab's own dict.  ValueError before any work for bad
+        edges, an undefined symbol or a syntax error."""
+        if where not in ("device", "host"):
+            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
+        spec = hist_spec(formula, bins, range, mask, variables)
+        d = self._histogram(spec, where, per_plane)
+        if d is None:
+            raise RuntimeError("histogram: no state is resident on the device (no initialised solver, or no "
+                               "fused solve or device IC yet); solve first, or use where='host'")
+        return d
+
+    def _hist_not_exact(self, spec):
+        """the text of the formula or mask that does not compile for the device, or None"""
+        for what, progs in (("formula", spec["value"]), ("mask", spec["masked"])):
+            if progs is not None and self._formula_not_exact(progs) is not None:
+                return spec[what]
+        return None
+
+    def _histogram(self, spec, where, per_plane):
+        """histogram() on a compiled spec (hist_spec); None when where="device" and nothing is
+        resident (pft_solver_hist's -3, the same on every rank)"""
+        edges = spec["edges"]
+        nbins, n3 = edges.size - 1, self.grid.n3
+        plane_heads = (pft_hist_head * n3)() if per_plane else None
+        plane_counts = (C.c_longlong * (n3 * nbins))() if per_plane else None
+        if where == "host":
+            (ghead, gcounts), (lhead, lcounts) = self._hist_host_global(spec, plane_heads, plane_counts)
+        else:
+            _, _, vops, vargs = spec["value"]
+            nm, mops, margs = 0, None, None
+            if spec["masked"] is not None:
+                _, _, mo, ma = spec["masked"]
+                nm, mops, margs = len(mo), _ip(mo), _dp(ma)
+            ghead, lhead = pft_hist_head(), pft_hist_head()
+            gcounts, lcounts = (C.c_longlong * nbins)(), (C.c_longlong * nbins)()
+            rc = self.lib.pft_solver_hist(len(vops), _ip(vops), _dp(vargs), nm, mops, margs, nbins, _dp(edges),
+                                          C.byref(ghead), gcounts, C.byref(lhead), lcounts, plane_heads, plane_counts)
+            if rc == -3:
+                return None
+            if rc == 1:
+                raise ValueError(f"histogram: {self._hist_not_exact(spec)!r} is not device-exact (pow or a libm "
+                                 "function, C or P over a field or several coordinates, or a stack deeper than "
+                                 "the device's); use where='host'")
+            if rc == -2:
+                raise ValueError("histogram: pft_solver_hist refused the programs or the edges (-2)")
+            if rc:
+                raise RuntimeError(f"pft_solver_hist failed ({rc}): {self.lib.pft_hip_last_error()}")
+
+        def as_dict(head, counts):
+            d = {"edges": edges.copy(), "counts": np.array(counts[:], dtype=np.int64)}
+            d.update(head.as_dict())
+            return d
+
+        d = as_dict(ghead, gcounts)
+        if per_plane:
+            d["counts_per_plane"] = np.array(plane_counts[:], dtype=np.int64).reshape(n3, nbins)
+            for k in HIST_ROW_KEYS:
+                d[k + "_per_plane"] = np.array([getattr(h, k) for h in plane_heads], dtype=np.int64)
+            d["first_row"] = self.grid.first_row
+            d["local"] = as_dict(lhead, lcounts)
+        return d
+
     # -- f7: snapshots from the resident state -----------------------------------------------------
     def _region(self, sel):
         """the pft_region of a selection (region()) on this simulation's grid; a pft_region is checked"""
@@ -1019,7 +1243,7 @@ class Simulation:
     def run_series(self, final_time=None, saved_files=None, times=None, snapshot_path=None, comment="",
                    diag=True, opts=None, means=False, snapshot_where="host", snapshot_async=False,
                    first_snapshot=0, total_snapshots=None, skip_first=False, regions=None, region_every=1,
-                   snapshot_full=True, formulas=None, variables=None):
+                   snapshot_full=True, formulas=None, variables=None, histograms=None):
         """The driver's snapshot loop (intertrack.c:2265-2283).  Snapshot 0 is the state as it
         stands (no solve); snapshot s solves to series_times(t0, final_time, saved_files)[s], or
         to times[s - 1] when times= lists the solve targets.  The steps run device-resident
@@ -1049,13 +1273,37 @@ class Simulation:
         the device-resident state, so that write_series_txt(rows, path, key="<name>_mean") writes its
         series.  The programs are compiled once, before the first solve; ValueError up front for a
         formula that is not device-exact and for a name whose keys would collide with a key of
-        diagnostics() or means()."""
+        diagnostics() or means().
+        histograms={name: {"formula": ..., "bins": ..., "range": ..., "mask": ...}} (f13; range and mask
+        optional, see histogram(); or hist_spec()'s result, compiled already): every row also carries
+        <name>, the counts (int64 [nbins]) over the whole grid from the device-resident state, and
+        <name>_under, _over, _nan and _selected, so that write_hist_txt(rows, path, key="<name>")
+        writes the series.  The specs are compiled once, before the first solve; ValueError up front
+        for bad edges, a formula or mask that is not device-exact and for a name whose keys collide
+        with another key of the rows.  All other row keys are unchanged."""
+        hists = None
+        if histograms is not None:
+            if not isinstance(histograms, dict) or not histograms:
+                raise ValueError("run_series: histograms= is a non-empty {name: spec} dict")
+            hists = {}
+            for name, sp in histograms.items():
+                if not isinstance(sp, dict) or not (sp.get("compiled") or {"formula", "bins"} <= set(sp)):
+                    raise ValueError(f"run_series: histogram {name!r} needs 'formula' and 'bins'")
+                if not sp.get("compiled"):
+                    extra = set(sp) - {"formula", "bins", "range", "mask"}
+                    if extra:
+                        raise ValueError(f"run_series: histogram {name!r} has unknown keys {sorted(extra)}")
+                    sp = hist_spec(sp["formula"], sp["bins"], sp.get("range"), sp.get("mask"), variables)
+                bad = self._hist_not_exact(sp)
+                if bad is not None:
+                    raise ValueError(f"run_series: histogram {name!r}: {bad!r} is not device-exact; evaluate it "
+                                     "with histogram(where='host') on a downloaded state")
+                hists[str(name)] = sp
         progs = None
         if formulas is not None:
             # (a tuple: programs compiled already by formula_programs, as Case.run passes them)
             progs = formulas if isinstance(formulas, tuple) else formula_programs(formulas, variables)
-            taken = ({"snapshot", "t", "h", "steps", "steps_total", "rc", "ice_fraction"}
-                     | {k for k, _ in pft_diag._fields_} | {k + s for k in MEAN_KEYS for s in ("_n", "_sum", "_mean")})
+            taken = self._series_keys()
             keys = [name + "_" + k for name in progs[0] for k in FORMULA_ROW_KEYS]
             clash = sorted(set(keys) & taken) + sorted({k for k in keys if keys.count(k) > 1})
             if clash:
@@ -1065,6 +1313,15 @@ class Simulation:
             if bad is not None:
                 raise ValueError(f"run_series: formula {bad!r} is not device-exact; evaluate it with "
                                  "formulas(where='host') on a downloaded state")
+        if hists is not None:
+            taken = self._series_keys()
+            if progs is not None:
+                taken |= {name + "_" + k for name in progs[0] for k in FORMULA_ROW_KEYS}
+            keys = [k for name in hists for k in [name] + [name + "_" + s for s in HIST_ROW_KEYS]]
+            clash = sorted(set(keys) & taken) + sorted({k for k in keys if keys.count(k) > 1})
+            if clash:
+                raise ValueError(f"run_series: the histogram keys {clash} collide with other keys of the rows; "
+                                 "rename the histogram")
         region_every = int(region_every)
         if region_every < 1:
             raise ValueError(f"region_every must be at least 1, not {region_every}")
@@ -1092,14 +1349,21 @@ class Simulation:
         try:
             rows = self._run_series(targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
                                     snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full,
-                                    progs)
+                                    progs, hists)
         finally:
             if self._snap_pending:
                 self.snapshot_wait()
         return rows
 
+    @staticmethod
+    def _series_keys():
+        """the row keys of run_series without formulas= and histograms="""
+        return ({"snapshot", "t", "h", "steps", "steps_total", "rc", "ice_fraction"}
+                | {k for k, _ in pft_diag._fields_} | {k + s for k in MEAN_KEYS for s in ("_n", "_sum", "_mean")})
+
     def _run_series(self, targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
-                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full, progs=None):
+                    snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full, progs=None,
+                    hists=None):
         rows = []
         for s, T in enumerate(targets, first):
             rc = None
@@ -1133,6 +1397,15 @@ class Simulation:
                                        "(the host-staged path keeps none)")
                 for name, rec in d.items():
                     row.update({name + "_" + k: rec[k] for k in FORMULA_ROW_KEYS})
+            for name, sp in (hists or {}).items():
+                d = self._histogram(sp, "device", False)
+                if d is None and s == first:
+                    d = self._histogram(sp, "host", False)
+                if d is None:
+                    raise RuntimeError("run_series: no state is resident on the device after the solve "
+                                       "(the host-staged path keeps none)")
+                row[name] = d["counts"]
+                row.update({name + "_" + k: d[k] for k in HIST_ROW_KEYS})
             if snapshot_path is not None and not (s == first and skip_first):
                 info = snapshot_info(self.system.t, self.system.h, end, self.system.delta, self.grid.calc_mode,
                                      snapshot=s, total_snapshots=total, comment=comment)

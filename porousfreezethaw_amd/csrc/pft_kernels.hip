@@ -2559,6 +2559,10 @@ int pft_slab_destroy(pft_slab* s)
   if (s->formula_prog_host) (void)hipHostFree(s->formula_prog_host);
   for (int i = 0; i < 2; ++i)
     if (s->ev_formula[i]) (void)hipEventDestroy(s->ev_formula[i]);
+  if (s->hist_dev) (void)hipFree(s->hist_dev);
+  if (s->hist_host) (void)hipHostFree(s->hist_host);
+  for (int i = 0; i < 2; ++i)
+    if (s->ev_hist[i]) (void)hipEventDestroy(s->ev_hist[i]);
   if (s->snap_host) {
     // the background writer may still read the image: it finishes first
     (void)pft_snapshot_writer_release(s->snap_host);

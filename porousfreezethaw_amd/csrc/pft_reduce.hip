@@ -1,9 +1,10 @@
 // pft_reduce.hip -- reductions over the resident state: the ice diagnostics (diag_kernel, f5) and
-// the exact means and z-profiles (means_kernel, f6), and the formula diagnostics (formula_kernel,
-// f12), with their host API.
+// the exact means and z-profiles (means_kernel, f6), the formula diagnostics (formula_kernel, f12)
+// and the histograms of formula values (hist_kernel, f13), with their host API.
 #include "pft_slab.h"
 
 #include "../../include/pft_formula.h"
+#include "../../include/pft_hist.h"
 #define PFT_IC_NO_CP   // no loop with a cell's value as its trip count is compiled into formula_kernel
 #include "pft_ic_ops.h"
 
@@ -919,22 +920,17 @@ static void formula_record(const unsigned long long* h, long long cells, pft_fdi
   memcpy(out->sum.w, h + FD_SUM, sizeof(out->sum.w));
 }
 
-extern "C" {
-
-int pft_slab_formulas(pft_slab* s, int buf, int nprog, const pft_ic_prog* progs, pft_fdiag* total, pft_fdiag* per_plane)
+// The programs of one call (f12: up to PFT_FORMULA_MAX; f13: the value and the mask) checked
+// before anything is launched: only what the device runs exactly and in bounded time (else 1: not
+// device-exact), a stack within the LDS column (else 1), a well-formed program with tables of this
+// slab's grid (else -2).  entries / tvals: the programs' entries and table values together.
+static int formula_progs_check(const pft_slab* s, int nprog, const pft_ic_prog* const* progs, long* entries_out,
+                               long* tvals_out)
 {
-  if (!s || !progs || !total || buf < 0 || buf >= PFT_BUF_COUNT || nprog < 1 || nprog > PFT_FORMULA_MAX) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_formulas");
-  const long plane = s->plane, n = (long)s->d.n3 * plane;
-  const int n3 = s->d.n3;
-  if (n > 0x7fffffffL || plane > PFT_MEANS_MAX_PLANE) return -2;
-  // every program checked before anything is launched: only what the device runs exactly and in
-  // bounded time (else 1: not device-exact), a stack within the LDS column (else 1), a well-formed
-  // program with tables of this slab's grid (else -2)
   long entries = 0, tvals = 0;
   bool inexact = false;
   for (int f = 0; f < nprog; ++f) {
-    const pft_ic_prog* p = &progs[f];
+    const pft_ic_prog* p = progs[f];
     if (p->n < 1 || !p->op || !p->arg || p->ntab < 0 || (p->ntab > 0 && (!p->tab_axis || !p->tab_off || !p->tab_val || !p->tab_err)))
       return -2;
     int depth = 0;
@@ -962,18 +958,27 @@ int pft_slab_formulas(pft_slab* s, int buf, int nprog, const pft_ic_prog* progs,
     for (int t = 0; t < p->ntab; ++t) {
       const int ax = p->tab_axis[t];
       const long len = (t + 1 < p->ntab ? p->tab_off[t + 1] : p->tab_len) - p->tab_off[t];
-      if (ax < 0 || ax > 2 || p->tab_off[t] < 0 || len != (ax == 0 ? s->d.n1 : (ax == 1 ? s->d.n2 : n3))) return -2;
+      if (ax < 0 || ax > 2 || p->tab_off[t] < 0 || len != (ax == 0 ? s->d.n1 : (ax == 1 ? s->d.n2 : s->d.n3))) return -2;
     }
     entries += p->n;
     tvals += p->ntab > 0 ? p->tab_len : 0;
   }
   if (entries > PFT_FORMULA_MAX_ENTRIES || tvals > 0x7fffffffL) return -2;
-  if (inexact) return 1;
-  // the blob: [arg][tval][code][meta][terr]
+  *entries_out = entries, *tvals_out = tvals;
+  return inexact ? 1 : 0;
+}
+
+// The checked programs packed into the slab's pinned blob, [arg][tval][code][meta][terr][extra]
+// (grown on demand, device and host): P points at the device copy's parts, *extra_dev at `extra`
+// bytes behind them on an 8-byte boundary (copied from extra_src: f13's edges), *bytes is what the
+// caller copies to the device on its stream.
+static int formula_progs_pack(pft_slab* s, int nprog, const pft_ic_prog* const* progs, long entries, long tvals,
+                              size_t extra, const void* extra_src, FormulaProgs* P, const char** extra_dev, size_t* bytes)
+{
   const size_t nv = (size_t)(tvals > 0 ? tvals : 1);
   const size_t o_arg = 0, o_val = o_arg + sizeof(double) * (size_t)entries, o_code = o_val + sizeof(double) * nv,
                o_meta = o_code + sizeof(int2) * (size_t)entries, o_err = o_meta + sizeof(int) * 3 * PFT_FORMULA_MAX,
-               blob = o_err + nv;
+               o_extra = (o_err + nv + 7) & ~(size_t)7, blob = extra ? o_extra + extra : o_err + nv;
   if (blob > s->formula_prog_cap) {
     const size_t cap = 2 * blob;
     if (s->formula_prog_dev) HIPCHK(hipFree(s->formula_prog_dev));
@@ -984,51 +989,71 @@ int pft_slab_formulas(pft_slab* s, int buf, int nprog, const pft_ic_prog* progs,
     HIPCHK(hipHostMalloc((void**)&s->formula_prog_host, cap, hipHostMallocDefault));
     s->formula_prog_cap = cap;
   }
-  {
-    char* h = s->formula_prog_host;
-    double* h_arg = (double*)(h + o_arg);
-    double* h_val = (double*)(h + o_val);
-    int2* h_code = (int2*)(h + o_code);
-    int* h_meta = (int*)(h + o_meta);
-    unsigned char* h_err = (unsigned char*)(h + o_err);
-    long c_at = 0, v_at = 0;
-    h_val[0] = 0.0, h_err[0] = 0;
-    for (int f = 0; f < nprog; ++f) {
-      const pft_ic_prog* p = &progs[f];
-      int need = 0;
-      h_meta[3 * f] = (int)c_at;
-      for (int c = 0; c < p->n; ++c, ++c_at) {
-        const int o = p->op[c];
-        h_arg[c_at] = p->arg[c];
-        h_code[c_at] = make_int2(o, 0);
-        if (o == 101) {
-          const int q = (int)p->arg[c] - 6;
-          h_code[c_at].y = q;
-          need |= 1 << q;
-        } else if (o == 102) {
-          const int t = (int)p->arg[c], ax = p->tab_axis[t];
-          h_code[c_at] = make_int2(102 + ax, (int)(v_at + p->tab_off[t]));
-          if (ax < 2) need |= FM_NEED_IJ;
-        }
-      }
-      h_meta[3 * f + 1] = (int)c_at;
-      h_meta[3 * f + 2] = need;
-      if (p->ntab > 0) {
-        memcpy(h_val + v_at, p->tab_val, sizeof(double) * (size_t)p->tab_len);
-        memcpy(h_err + v_at, p->tab_err, (size_t)p->tab_len);
-        v_at += p->tab_len;
+  char* h = s->formula_prog_host;
+  double* h_arg = (double*)(h + o_arg);
+  double* h_val = (double*)(h + o_val);
+  int2* h_code = (int2*)(h + o_code);
+  int* h_meta = (int*)(h + o_meta);
+  unsigned char* h_err = (unsigned char*)(h + o_err);
+  long c_at = 0, v_at = 0;
+  h_val[0] = 0.0, h_err[0] = 0;
+  for (int f = 0; f < nprog; ++f) {
+    const pft_ic_prog* p = progs[f];
+    int need = 0;
+    h_meta[3 * f] = (int)c_at;
+    for (int c = 0; c < p->n; ++c, ++c_at) {
+      const int o = p->op[c];
+      h_arg[c_at] = p->arg[c];
+      h_code[c_at] = make_int2(o, 0);
+      if (o == 101) {
+        const int q = (int)p->arg[c] - 6;
+        h_code[c_at].y = q;
+        need |= 1 << q;
+      } else if (o == 102) {
+        const int t = (int)p->arg[c], ax = p->tab_axis[t];
+        h_code[c_at] = make_int2(102 + ax, (int)(v_at + p->tab_off[t]));
+        if (ax < 2) need |= FM_NEED_IJ;
       }
     }
+    h_meta[3 * f + 1] = (int)c_at;
+    h_meta[3 * f + 2] = need;
+    if (p->ntab > 0) {
+      memcpy(h_val + v_at, p->tab_val, sizeof(double) * (size_t)p->tab_len);
+      memcpy(h_err + v_at, p->tab_err, (size_t)p->tab_len);
+      v_at += p->tab_len;
+    }
   }
+  if (extra) memcpy(h + o_extra, extra_src, extra);
+  P->arg = (const double*)(s->formula_prog_dev + o_arg);
+  P->tval = (const double*)(s->formula_prog_dev + o_val);
+  P->code = (const int2*)(s->formula_prog_dev + o_code);
+  P->meta = (const int*)(s->formula_prog_dev + o_meta);
+  P->terr = (const unsigned char*)(s->formula_prog_dev + o_err);
+  if (extra_dev) *extra_dev = s->formula_prog_dev + o_extra;
+  *bytes = blob;
+  return 0;
+}
+
+extern "C" {
+
+int pft_slab_formulas(pft_slab* s, int buf, int nprog, const pft_ic_prog* progs, pft_fdiag* total, pft_fdiag* per_plane)
+{
+  if (!s || !progs || !total || buf < 0 || buf >= PFT_BUF_COUNT || nprog < 1 || nprog > PFT_FORMULA_MAX) return -2;
+  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_formulas");
+  const long plane = s->plane, n = (long)s->d.n3 * plane;
+  const int n3 = s->d.n3;
+  if (n > 0x7fffffffL || plane > PFT_MEANS_MAX_PLANE) return -2;
+  const pft_ic_prog* list[PFT_FORMULA_MAX];
+  for (int f = 0; f < nprog; ++f) list[f] = &progs[f];
+  long entries = 0, tvals = 0;
+  int rc_pack = formula_progs_check(s, nprog, list, &entries, &tvals);
+  if (rc_pack) return rc_pack;
+  FormulaProgs P;
+  size_t blob = 0;
+  if ((rc_pack = formula_progs_pack(s, nprog, list, entries, tvals, 0, nullptr, &P, nullptr, &blob))) return rc_pack;
   const size_t words = (size_t)FD_REC * (PFT_FORMULA_MAX + (size_t)PFT_FORMULA_MAX * n3);
   if (!s->formula_dev) HIPCHK(hipMalloc((void**)&s->formula_dev, sizeof(unsigned long long) * words));
   if (!s->formula_host) HIPCHK(hipHostMalloc((void**)&s->formula_host, sizeof(unsigned long long) * words, hipHostMallocDefault));
-  FormulaProgs P;
-  P.arg = (const double*)(s->formula_prog_dev + o_arg);
-  P.tval = (const double*)(s->formula_prog_dev + o_val);
-  P.code = (const int2*)(s->formula_prog_dev + o_code);
-  P.meta = (const int*)(s->formula_prog_dev + o_meta);
-  P.terr = (const unsigned char*)(s->formula_prog_dev + o_err);
   // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
   const double* fu = s->buf[buf] + plane;
   const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
@@ -1080,6 +1105,320 @@ int pft_slab_formulas_last_ms(pft_slab* s, double* ms)
   if (!s || !ms || !s->formula_timing) return -2;
   float f = 0.0f;
   HIPCHK(hipEventElapsedTime(&f, s->ev_formula[0], s->ev_formula[1]));
+  *ms = f;
+  return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// f13: histograms of formula values (pft_hist.h) -- formula_kernel's traversal and interpreter, but
+// what is reduced is a count per bin.  Program 0 of the blob is the value, program 1 (when there is
+// one) the mask; a cell's mask and then its value are evaluated by formula_eval on the same LDS
+// stack column, with the wave's program counter: unselected lanes run along and are left out of
+// every count.  The edges are copied into LDS once per workgroup; a selected value's bin is the
+// number of edges <= v, less one, found by a binary search without branches whose trip count
+// `trips` = ceil(log2(nbins + 1)) is a kernel argument -- no loop depends on a cell's value.
+//
+// Counts are integers only.  selected / nan / under / over go by ballot and popcount in scalar
+// registers.  Bin counts go to 32-bit LDS counters (an item is at most a plane, <= 2^30 cells).
+// The usual state of this model has almost every cell in one bin (u = 293.15 over most of the
+// domain, p at 0 or 1), so a wave first aggregates equal bins: PFT_HIST_ROUNDS times (once: measured) it takes the
+// bin of its first remaining lane, ballots the lanes that share it and lets that lane add the
+// popcount; the lanes still left add 1 each (ds_add_u32).  At the end of an item one thread per
+// non-zero word adds it to the plane's row in global memory (64-bit integer atomicAdd) and zeroes
+// the LDS word; hist_total_kernel adds the planes' rows into the slab's.  No floating-point
+// atomic, no compare-and-swap, no spin.
+//
+// LDS: 30 720 (stack) + 8 200 (edges) + 4 096 (counters) + 32 (head) bytes.
+#ifndef PFT_HIST_ROUNDS
+#define PFT_HIST_ROUNDS 1   // (scripts/hist_time.py on builds with 0, 1, 2 and 4: DESIGN.md section 7, f13)
+#endif
+enum { HD_SELECTED = 0, HD_NAN, HD_UNDER, HD_OVER, HD_WORDS };
+
+struct HistState {
+  unsigned long long selected, nan, under, over;   // wave-uniform counts
+};
+
+// one iteration of a wave, as formula_iter (full: every slot of the 512 belongs to the item): c0..c1
+// the value's entries, m0..m1 the mask's (m0 == m1: no mask), need the fields and indices either
+// program pushes.  The interpreter is compiled into the kernel once: the full and the ragged
+// iteration differ in their loads only, and the two elements of a pair and the two programs take
+// turns through the same copy (loops that are not unrolled) -- eight inlined copies are more code
+// than the instruction cache holds.
+__device__ __forceinline__ void hist_iter(HistState& st, const FormulaProgs& P, int c0, int c1, int m0, int m1, int need,
+                                          bool full, const double* __restrict__ fu, const double* __restrict__ fp,
+                                          const double* __restrict__ fg, int r0, int r_lo, int r_hi, int first,
+                                          int n1, int k, int lane, double* stack, const double* s_edges,
+                                          unsigned* s_cnt, int nbins, int trips, double e_first, double e_last)
+{
+#pragma unroll 1
+  for (int jj = 0; jj < PFT_DIAG_UNROLL; ++jj) {
+    const int r = r0 + 128 * jj + 2 * lane;
+    double u[2] = {0.0, 0.0}, p[2] = {0.0, 0.0}, g[2] = {0.0, 0.0};
+    bool v[2];
+    if (full) {
+      if (need & FM_NEED_U) {
+        const double2 a = *reinterpret_cast<const double2*>(fu + r);
+        u[0] = a.x, u[1] = a.y;
+      }
+      if (need & FM_NEED_P) {
+        const double2 a = *reinterpret_cast<const double2*>(fp + r);
+        p[0] = a.x, p[1] = a.y;
+      }
+      if (need & FM_NEED_GL) {
+        const double2 a = *reinterpret_cast<const double2*>(fg + r);
+        g[0] = a.x, g[1] = a.y;
+      }
+      v[0] = v[1] = true;
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const bool ok = r + h >= r_lo && r + h < r_hi;
+        v[h] = ok;
+        if (ok && (need & FM_NEED_U)) u[h] = fu[r + h];
+        if (ok && (need & FM_NEED_P)) p[h] = fp[r + h];
+        if (ok && (need & FM_NEED_GL)) g[h] = fg[r + h];
+      }
+    }
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const double uh = h ? u[1] : u[0], ph = h ? p[1] : p[0], gh = h ? g[1] : g[0];
+      const bool vh = h ? v[1] : v[0];
+      // the node's place in its plane; a slot outside the item evaluates node 0 (inside every
+      // table) and is left out of every count below
+      const int e = vh ? first + (r + h - r_lo) : 0;
+      int i = 0, j = 0;
+      if (need & FM_NEED_IJ) {
+        j = e / n1;
+        i = e - j * n1;
+      }
+      bool sel = vh;
+      double x = 0.0;
+#pragma unroll 1
+      for (int pass = m1 > m0 ? 0 : 1; pass < 2; ++pass) {
+        const double val = formula_eval(P, pass ? c0 : m0, pass ? c1 : m1, uh, ph, gh, i, j, k, stack);
+        if (pass == 0)
+          sel = sel && val != 0;   // (a NaN is "true")
+        else
+          x = val;
+      }
+      // pos: the number of edges <= x (0 for a NaN); every lane makes the same `trips` steps
+      int pos = 0;
+      // (index clamped and both tests combined bitwise: one ds_read_b64, compares and a shift per
+      // step, no exec-mask branch)
+      for (int t = trips - 1; t >= 0; --t) {
+        const int at = pos + (1 << t) - 1;
+        const double ed = s_edges[at < nbins ? at : nbins];
+        pos += (int)((unsigned)(at <= nbins) & (unsigned)(ed <= x)) << t;
+      }
+      const bool is_nan = sel && x != x, is_under = sel && x < e_first, is_over = sel && x > e_last;
+      const bool binned = sel && x >= e_first && x <= e_last;      // (ordered: false on NaN)
+      const int b = pos > nbins ? nbins - 1 : pos - 1;             // x == the last edge: the last bin
+      st.selected += __popcll(__ballot(sel));
+      st.nan += __popcll(__ballot(is_nan));
+      st.under += __popcll(__ballot(is_under));
+      st.over += __popcll(__ballot(is_over));
+      unsigned long long rem = __ballot(binned);
+#pragma unroll
+      for (int round = 0; round < PFT_HIST_ROUNDS; ++round) {
+        if (!rem) break;
+        const int lead = (int)__ffsll((long long)rem) - 1;
+        const int lb = __builtin_amdgcn_readlane(b, lead);
+        const unsigned long long same = __ballot(binned && b == lb) & rem;
+        if (lane == lead) atomicAdd(&s_cnt[lb], (unsigned)__popcll(same));
+        rem &= ~same;
+      }
+      if ((rem >> lane) & 1) atomicAdd(&s_cnt[b], 1u);
+    }
+  }
+}
+
+// rec: rows of `row` = HD_WORDS + nbins words: row 0 the slab's (written by hist_total_kernel), row
+// 1 + k interior plane k's
+__global__ __launch_bounds__(PFT_DBLOCK) void hist_kernel(const double* __restrict__ fu, const double* __restrict__ fp,
+                                                          const double* __restrict__ fg, int plane, int head, int n1,
+                                                          int n3, int segs, int seg_len, FormulaProgs P, int has_mask,
+                                                          const double* __restrict__ edges, int nbins, int trips,
+                                                          unsigned long long* __restrict__ rec)
+{
+  __shared__ double s_stack[PFT_FORMULA_SLOTS * PFT_DBLOCK];
+  __shared__ double s_edges[PFT_HIST_MAX_BINS + 1];
+  __shared__ unsigned s_cnt[PFT_HIST_MAX_BINS];
+  __shared__ unsigned long long s_head[HD_WORDS];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c0 = P.meta[0], c1 = P.meta[1];
+  const int m0 = has_mask ? P.meta[3] : 0, m1 = has_mask ? P.meta[4] : 0;
+  const int need = P.meta[2] | (has_mask ? P.meta[5] : 0);
+  for (int i = threadIdx.x; i <= nbins; i += PFT_DBLOCK) s_edges[i] = edges[i];
+  for (int i = threadIdx.x; i < nbins; i += PFT_DBLOCK) s_cnt[i] = 0;
+  if (threadIdx.x < HD_WORDS) s_head[threadIdx.x] = 0;
+  __syncthreads();
+  const double e_first = s_edges[0], e_last = s_edges[nbins];
+  const int row = HD_WORDS + nbins;
+  HistState st;
+  double* stack = s_stack + threadIdx.x;
+  const long items = (long)n3 * segs;
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    const int k = (int)(item / segs), j = (int)(item - (long)k * segs);
+    const int first = j * seg_len;                                    // within the plane
+    const int len = plane - first < seg_len ? plane - first : seg_len;
+    const long a = (long)k * plane + first;                           // within the run of n3 planes
+    // the frame of means_kernel: e_base on a 16-byte boundary at or one below a
+    const long e_base = 2 * ((a + head) >> 1) - head;
+    const int r_lo = (int)(a - e_base), r_hi = r_lo + len;
+    const int span = (r_hi + 1) & ~1;
+    const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
+    const double* wp = fp + e_base;
+    const double* wg = fg + e_base;
+    st.selected = st.nan = st.under = st.over = 0;
+    for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
+      hist_iter(st, P, c0, c1, m0, m1, need, r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi, wu, wp, wg, r0, r_lo, r_hi,
+                first, n1, k, lane, stack, s_edges, s_cnt, nbins, trips, e_first, e_last);
+    }
+    if (lane == 0) {
+      if (st.selected) atomicAdd(&s_head[HD_SELECTED], st.selected);
+      if (st.nan) atomicAdd(&s_head[HD_NAN], st.nan);
+      if (st.under) atomicAdd(&s_head[HD_UNDER], st.under);
+      if (st.over) atomicAdd(&s_head[HD_OVER], st.over);
+    }
+    __syncthreads();
+    // one thread per word: the non-zero ones to the plane's row, and the LDS copy zeroed again
+    unsigned long long* dst = rec + (size_t)(k + 1) * row;
+    for (int i = threadIdx.x; i < row; i += PFT_DBLOCK) {
+      if (i < HD_WORDS) {
+        const unsigned long long x = s_head[i];
+        if (x) {
+          atomicAdd(&dst[i], x);
+          s_head[i] = 0;
+        }
+      } else {
+        const unsigned x = s_cnt[i - HD_WORDS];
+        if (x) {
+          atomicAdd(&dst[i], (unsigned long long)x);
+          s_cnt[i - HD_WORDS] = 0;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the slab's row = the word-wise sum of the planes': per word four threads, each a quarter of the
+// planes, then one of them stores the sum (no atomics: nobody else writes row 0)
+__global__ __launch_bounds__(256) void hist_total_kernel(unsigned long long* __restrict__ rec, int n3, int row)
+{
+  __shared__ unsigned long long s_part[4][64];
+  const int l = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int w = blockIdx.x * 64 + l;
+  unsigned long long x = 0;
+  if (w < row)
+    for (int k = q; k < n3; k += 4) x += rec[(size_t)(k + 1) * row + w];
+  s_part[q][l] = x;
+  __syncthreads();
+  if (q == 0 && w < row) rec[w] = s_part[0][l] + s_part[1][l] + s_part[2][l] + s_part[3][l];
+}
+
+// a device row's words as a record of `cells` cells
+static void hist_record(const unsigned long long* h, long long cells, int nbins, pft_hist_head* head, long long* counts)
+{
+  if (head) {
+    head->cells = cells;
+    head->selected = (long long)h[HD_SELECTED];
+    head->nan = (long long)h[HD_NAN];
+    head->under = (long long)h[HD_UNDER];
+    head->over = (long long)h[HD_OVER];
+  }
+  if (counts) memcpy(counts, h + HD_WORDS, sizeof(long long) * (size_t)nbins);
+}
+
+extern "C" {
+
+int pft_slab_hist(pft_slab* s, int buf, const pft_ic_prog* value_prog, const pft_ic_prog* mask_prog, int nbins,
+                  const double* edges, pft_hist_head* head, long long* counts, pft_hist_head* plane_heads,
+                  long long* plane_counts)
+{
+  if (!s || !value_prog || !head || !counts || buf < 0 || buf >= PFT_BUF_COUNT) return -2;
+  if (pft_hist_check(nbins, edges)) return -2;
+  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_hist");
+  const long plane = s->plane, n = (long)s->d.n3 * plane;
+  const int n3 = s->d.n3;
+  if (n > 0x7fffffffL || plane > PFT_MEANS_MAX_PLANE) return -2;
+  const pft_ic_prog* list[2] = {value_prog, mask_prog};
+  const int nprog = mask_prog ? 2 : 1;
+  long entries = 0, tvals = 0;
+  int rc_pack = formula_progs_check(s, nprog, list, &entries, &tvals);
+  if (rc_pack) return rc_pack;
+  FormulaProgs P;
+  const char* edges_dev = nullptr;
+  size_t blob = 0;
+  if ((rc_pack = formula_progs_pack(s, nprog, list, entries, tvals, sizeof(double) * ((size_t)nbins + 1), edges, &P,
+                                    &edges_dev, &blob)))
+    return rc_pack;
+  const int row = HD_WORDS + nbins;
+  const size_t bytes = sizeof(unsigned long long) * (size_t)row * ((size_t)n3 + 1);
+  if (bytes > s->hist_cap) {
+    if (s->hist_dev) HIPCHK(hipFree(s->hist_dev));
+    if (s->hist_host) HIPCHK(hipHostFree(s->hist_host));
+    s->hist_dev = s->hist_host = nullptr;
+    s->hist_cap = 0;
+    HIPCHK(hipMalloc((void**)&s->hist_dev, bytes));
+    HIPCHK(hipHostMalloc((void**)&s->hist_host, bytes, hipHostMallocDefault));
+    s->hist_cap = bytes;
+  }
+  int trips = 0;   // ceil(log2(nbins + 1)): the first power of two that is >= the number of edges
+  while ((1 << trips) < nbins + 1) ++trips;
+  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
+  const double* fu = s->buf[buf] + plane;
+  const int head_odd = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
+  // pft_slab_means' cut of the planes into work items
+  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
+  const long wg_elems = 2L * PFT_DIAG_WG_PAIRS;
+  long want = cap / n3;
+  if (want < 1) want = 1;
+  const long seg_len = ((plane + want - 1) / want + wg_elems - 1) / wg_elems * wg_elems;
+  const long segs = (plane + seg_len - 1) / seg_len;
+  const long items = segs * n3;
+  const long wgs = items < cap ? items : cap;
+  HIPCHK(hipMemcpyAsync(s->formula_prog_dev, s->formula_prog_host, blob, hipMemcpyHostToDevice, s->stream));
+  // no state carries over between calls: every accumulator word is zeroed on the stream first
+  HIPCHK(hipMemsetAsync(s->hist_dev, 0, bytes, s->stream));
+  if (s->hist_timing) HIPCHK(hipEventRecord(s->ev_hist[0], s->stream));
+  hist_kernel<<<(unsigned)wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head_odd, s->d.n1, n3,
+                                                           (int)segs, (int)seg_len, P, mask_prog ? 1 : 0,
+                                                           (const double*)edges_dev, nbins, trips, s->hist_dev);
+  HIPCHK(hipGetLastError());
+  hist_total_kernel<<<(row + 63) / 64, 256, 0, s->stream>>>(s->hist_dev, n3, row);
+  HIPCHK(hipGetLastError());
+  if (s->hist_timing) HIPCHK(hipEventRecord(s->ev_hist[1], s->stream));
+  const bool planes = plane_heads || plane_counts;
+  const size_t back = planes ? bytes : sizeof(unsigned long long) * (size_t)row;
+  HIPCHK(hipMemcpyAsync(s->hist_host, s->hist_dev, back, hipMemcpyDeviceToHost, s->stream));
+  const int rc = slab_wait(s, nullptr, "pft_slab_hist");
+  if (rc) return rc;
+  hist_record(s->hist_host, n, nbins, head, counts);
+  if (planes)
+    for (int k = 0; k < n3; ++k)
+      hist_record(s->hist_host + (size_t)(k + 1) * row, plane, nbins, plane_heads ? &plane_heads[k] : nullptr,
+                  plane_counts ? plane_counts + (size_t)k * nbins : nullptr);
+  return 0;
+}
+
+int pft_slab_hist_timing(pft_slab* s, int on)
+{
+  if (!s) return -2;
+  for (int i = 0; i < 2 && on; ++i)
+    if (!s->ev_hist[i]) HIPCHK(hipEventCreate(&s->ev_hist[i]));
+  s->hist_timing = on ? 1 : 0;
+  return 0;
+}
+
+int pft_slab_hist_last_ms(pft_slab* s, double* ms)
+{
+  if (!s || !ms || !s->hist_timing) return -2;
+  float f = 0.0f;
+  HIPCHK(hipEventElapsedTime(&f, s->ev_hist[0], s->ev_hist[1]));
   *ms = f;
   return 0;
 }

@@ -4,7 +4,7 @@
 // kernels' template arguments.  The translation units over the C ABI of include/pft_hip.h:
 //   pft_kernels.hip  the step kernels (merson_stage, merson_fused, merson_pair), the slab object's
 //                    API, the pft_hip_* shim, the halo exchange, IC
-//   pft_reduce.hip   diagnostics, exact means and formula diagnostics (f5, f6, f12)
+//   pft_reduce.hip   diagnostics, exact means, formula diagnostics and histograms (f5, f6, f12, f13)
 //   pft_snap.hip     snapshots (f7), region snapshots (f11)
 // No device code crosses files: nothing is device-linked.  Every .hip includes this header first.
 #pragma once
@@ -210,6 +210,14 @@ struct pft_slab {
   size_t formula_prog_cap;
   int formula_timing;
   hipEvent_t ev_formula[2];
+  // f13 histograms (pft_slab_hist): the slab's row of 4 + nbins words, then one row per interior
+  // plane, and their pinned host copy, grown on demand (hist_cap bytes each); the programs and the
+  // edges travel in the f12 blob; events around the kernel pair
+  unsigned long long* hist_dev;
+  unsigned long long* hist_host;     // pinned
+  size_t hist_cap;
+  int hist_timing;
+  hipEvent_t ev_hist[2];
   // f7 snapshots (pft_slab_snapshot_export / pft_slab_image): the image-sized pinned, host-mapped
   // buffer the background writer reads (allocated by the first call, freed at destroy once the
   // writer is done with it), the device staging image of the staged host link, events around the

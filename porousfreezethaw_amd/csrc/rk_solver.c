@@ -21,6 +21,7 @@
 #include "pft_internal.h"
 #include "../../include/pft_frontend.h"
 #include "../../include/pft_formula.h"
+#include "../../include/pft_hist.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -899,6 +900,142 @@ int pft_solver_formulas(int nprog, const int * lens, const int * ops, const doub
 		if(local) local[f] = mine.d[f];
 	}
 	free(all);
+	return 0;
+}
+
+/* FNV-1a over a run of bytes, continued from h */
+static unsigned long long hist_hash(unsigned long long h, const void * p, size_t n)
+{
+	const unsigned char * b = (const unsigned char *)p;
+	size_t i;
+	for(i = 0; i < n; i++) { h ^= b[i]; h *= 0x100000001b3ULL; }
+	return h;
+}
+
+int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, const int * mops, const double * margs,
+                    int nbins, const double * edges, pft_hist_head * global, long long * global_counts,
+                    pft_hist_head * local, long long * local_counts, pft_hist_head * plane_heads,
+                    long long * plane_counts)
+{
+	/* f13: the histogram of the device-resident x, under pft_solver_diag's rules.  Every rank checks
+	   the edges and compiles both programs first; the outcome (1 not device-exact, -2 a bad program
+	   or bad edges, the same on every rank; -1 out of memory, local: -1 over -2 over 1) and a 64-bit
+	   hash of nbins, the edges and both programs travel in the first allgather round, so that ranks
+	   that were given different histograms all answer -2 before any device work.  Then each rank
+	   counts its slab and the record travels with its status in rounds of at most 256 bytes, as
+	   pft_solver_formulas' do; the records are merged in rank order */
+	enum { ROUND = 256 };
+	struct hist_first { long long code; unsigned long long hash; };
+	struct hist_msg { long long status; pft_hist_head h; long long counts[PFT_HIST_MAX_BINS]; };
+	struct hist_msg * all, * mine;   /* (loopback ranks are threads of one process: nothing static) */
+	char piece[PFT_DIAG_MAX_RANKS * ROUND];
+	struct hist_first first, firsts[PFT_DIAG_MAX_RANKS];
+	pft_ic_prog pv, pm;
+	pft_grid g;
+	pft_comm * c = comm();
+	const int nprocs = pft_comm_size(c);
+	const int masked = mops || margs || nm;
+	int rc = 0, r, bad = 0, first_bad = 0;
+	long long my_status = 0;
+	size_t at, used;
+	if(!global || !global_counts) return -2;
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if(R.in_callback && nprocs > 1) return -2;
+	if(nprocs > PFT_DIAG_MAX_RANKS) return -2;
+	memset(&pv, 0, sizeof pv);
+	memset(&pm, 0, sizeof pm);
+	first.hash = 0xcbf29ce484222325ULL;
+	if(nv < 1 || nv > PFT_FORMULA_MAX_ENTRIES || !vops || !vargs || pft_hist_check(nbins, edges)
+	   || (masked && (nm < 1 || !mops || !margs || nv + nm > PFT_FORMULA_MAX_ENTRIES)) || pft_model_get_grid(&g)) rc = -2;
+	if(!rc) {
+		first.hash = hist_hash(first.hash, &nbins, sizeof nbins);
+		first.hash = hist_hash(first.hash, edges, sizeof(double) * ((size_t)nbins + 1));
+		first.hash = hist_hash(first.hash, &nv, sizeof nv);
+		first.hash = hist_hash(first.hash, vops, sizeof(int) * (size_t)nv);
+		first.hash = hist_hash(first.hash, vargs, sizeof(double) * (size_t)nv);
+		first.hash = hist_hash(first.hash, &nm, sizeof nm);
+		if(masked) {
+			first.hash = hist_hash(first.hash, mops, sizeof(int) * (size_t)nm);
+			first.hash = hist_hash(first.hash, margs, sizeof(double) * (size_t)nm);
+		}
+		rc = pft_formula_compile(&g, nv, vops, vargs, &pv);
+		if(!rc && masked) rc = pft_formula_compile(&g, nm, mops, margs, &pm);
+	}
+	if(nprocs > 1) {
+		int crc;
+		long long v = 0;
+		first.code = rc == -1 ? 3 : (rc == -2 ? 2 : (rc == 1 ? 1 : (rc ? 3 : 0)));
+		crc = pft_comm_allgather(c, &first, (int)sizeof first, firsts);
+		if(crc) {
+			pft_ic_prog_free(&pv);
+			pft_ic_prog_free(&pm);
+			R.last_status = crc;
+			return PFT_SOLVE_DEVICE_ERROR;
+		}
+		for(r = 0; r < nprocs; r++) if(firsts[r].code > v) v = firsts[r].code;
+		/* (ranks that all compiled: the same histogram on every one of them, or -2) */
+		for(r = 1; r < nprocs && !v; r++) if(firsts[r].hash != firsts[0].hash) v = 2;
+		rc = v == 3 ? -1 : (v == 2 ? -2 : (v == 1 ? 1 : 0));
+	}
+	if(rc) {
+		pft_ic_prog_free(&pv);
+		pft_ic_prog_free(&pm);
+		return rc;
+	}
+	mine = (struct hist_msg *)calloc(1, sizeof *mine);
+	if(mine) rc = pft_slab_hist(R.slab, PFT_BUF_X, &pv, masked ? &pm : NULL, nbins, edges, &mine->h, mine->counts,
+	                            plane_heads, plane_counts);
+	pft_ic_prog_free(&pv);
+	pft_ic_prog_free(&pm);
+	if(nprocs == 1) {
+		if(!mine) return -1;
+		if(rc) { free(mine); R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
+		*global = mine->h;
+		memcpy(global_counts, mine->counts, sizeof(long long) * (size_t)nbins);
+		if(local) *local = mine->h;
+		if(local_counts) memcpy(local_counts, mine->counts, sizeof(long long) * (size_t)nbins);
+		free(mine);
+		return 0;
+	}
+	used = offsetof(struct hist_msg, counts) + (size_t)nbins * sizeof(long long);
+	/* (a failed allocation is this rank's failure, met after the rounds like any other) */
+	all = (struct hist_msg *)malloc((size_t)nprocs * sizeof *all);
+	for(at = 0; at < used; at += ROUND) {
+		const int bytes = (int)(used - at < ROUND ? used - at : ROUND);
+		char out[ROUND];
+		memset(out, 0, sizeof out);
+		if(mine) memcpy(out, (const char *)mine + at, bytes);
+		if(at == 0) {
+			my_status = !mine || !all ? (rc ? rc : -1) : rc;
+			memcpy(out, &my_status, sizeof my_status);
+		}
+		if((rc = pft_comm_allgather(c, out, bytes, piece))) {
+			free(all);
+			free(mine);
+			R.last_status = rc;
+			return PFT_SOLVE_DEVICE_ERROR;
+		}
+		if(at == 0)
+			for(r = 0; r < nprocs; r++) {
+				long long st;
+				memcpy(&st, piece + (size_t)r*bytes, sizeof st);
+				if(st) { bad = 1; if(!first_bad) first_bad = (int)st; }
+			}
+		for(r = 0; r < nprocs && all; r++) memcpy((char *)&all[r] + at, piece + (size_t)r*bytes, bytes);
+	}
+	if(bad) {
+		free(all);
+		free(mine);
+		R.last_status = my_status ? (int)my_status : first_bad;
+		return PFT_SOLVE_DEVICE_ERROR;
+	}
+	*global = all[0].h;
+	memcpy(global_counts, all[0].counts, sizeof(long long) * (size_t)nbins);
+	for(r = 1; r < nprocs; r++) pft_hist_combine(nbins, global, global_counts, &all[r].h, all[r].counts);
+	if(local) *local = mine->h;
+	if(local_counts) memcpy(local_counts, mine->counts, sizeof(long long) * (size_t)nbins);
+	free(all);
+	free(mine);
 	return 0;
 }
 
