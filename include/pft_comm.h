@@ -27,6 +27,7 @@
 #ifndef PFT_COMM_H
 #define PFT_COMM_H
 
+#include <stddef.h>
 #include "pft_hip.h"
 
 #ifdef __cplusplus
@@ -114,6 +115,13 @@ int pft_comm_bcast(pft_comm * c, void * data, int bytes, int root);
    ncclAllGather on the communication stream through pinned host memory (its bounded, watched
    wait); a single rank copies.  PFT_ERR_COMM_ABORTED on an aborted communicator, -2 bad arguments. */
 int pft_comm_allgather(pft_comm * c, const void * mine, int bytes, void * all);
+/* a message of any length: every rank's `bytes` end up contiguous at all[rank * bytes ...], moved in
+   pft_comm_allgather rounds of at most 256 bytes (the first 256, the next 256, ..., a short last
+   round), the one place that makes these rounds.  all == NULL takes part in every round and discards
+   what arrives: what a rank whose allocation failed does, so that no other rank is left inside a
+   collective.  A failing round returns its code at once; a single rank copies.  -2: bad arguments,
+   more than 64 ranks. */
+int pft_comm_allgather_any(pft_comm * c, const void * mine, size_t bytes, void * all);
 int pft_comm_allreduce_max_i64(pft_comm * c, long long * v);
 int pft_comm_barrier(pft_comm * c);
 

@@ -56,8 +56,8 @@ int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * lo
    record, the same words on every rank; local (optional): this slab's; per_plane (optional, this
    slab's n3 records): one record per plane, global rows first_row + k.  Collective on several
    ranks: each rank reduces its slab (pft_slab_means) and its 2 144-byte record travels with its
-   status in as many pft_comm_allgather rounds of at most 256 bytes as that takes (9); the records
-   are merged in rank order, every rank returns the same code. */
+   status by pft_comm_allgather_any (pft_comm.h: 9 rounds); the records are merged in rank order,
+   every rank returns the same code. */
 int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means * local, pft_means * per_plane);
 
 /* f12: the formula diagnostics (pft_formula.h) of the device-resident x, under the rules of
@@ -70,9 +70,8 @@ int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means *
    for a bad program or limits exceeded, the same on every rank.  global: nprog records of the whole
    grid, the same bits on every rank; local (optional): this slab's; per_plane (optional, n3 * nprog
    records): entry f * n3 + k is program f's record of this slab's plane k.  Collective on several
-   ranks: each rank reduces its slab (pft_slab_formulas) and its records travel with its status in
-   pft_comm_allgather rounds of at most 256 bytes; they are merged in rank order and every rank
-   returns the same code. */
+   ranks: each rank reduces its slab (pft_slab_formulas) and its records travel with its status by
+   pft_comm_allgather_any; they are merged in rank order and every rank returns the same code. */
 int pft_solver_formulas(int nprog, const int * lens, const int * ops, const double * args, pft_fdiag * global,
                         pft_fdiag * local, pft_fdiag * per_plane);
 
@@ -89,9 +88,8 @@ int pft_solver_formulas(int nprog, const int * lens, const int * ops, const doub
    work.  global / global_counts[nbins]: the record of the whole grid, the same bits on every rank;
    local / local_counts (optional): this slab's; plane_heads (optional, n3 heads) and plane_counts
    (optional, n3 * nbins): this slab's planes'.  Collective on several ranks: each rank counts its
-   slab (pft_slab_hist) and its record travels with its status in pft_comm_allgather rounds of at
-   most 256 bytes (33 for 1024 bins); the records are merged in rank order and every rank returns
-   the same code. */
+   slab (pft_slab_hist) and its record travels with its status by pft_comm_allgather_any (33 rounds
+   for 1024 bins); the records are merged in rank order and every rank returns the same code. */
 int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, const int * mops, const double * margs,
                     int nbins, const double * edges, pft_hist_head * global, long long * global_counts,
                     pft_hist_head * local, long long * local_counts, pft_hist_head * plane_heads,

@@ -447,6 +447,7 @@ def lib():
         L.pft_slab_means_last_ms.argtypes = [C.c_void_p, dp]
         L.pft_solver_means.argtypes = [op, mp, mp, mp]
         L.pft_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.pft_comm_allgather_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         fp, icp = C.POINTER(pft_fdiag), C.POINTER(pft_ic_prog)
         L.pft_fdiag_init.argtypes = [fp]
         L.pft_fdiag_init.restype = None
@@ -572,6 +573,11 @@ def region(k, j, i, grid):
             start, step, count = start % n, 1, 1
         r.start[2 - axis], r.count[2 - axis], r.stride[2 - axis] = start, count, step
     return r
+
+
+def _check_where(where):
+    if where not in ("device", "host"):
+        raise ValueError(f"where must be 'device' or 'host', not {where!r}")
 
 
 def params_array(values):
@@ -795,6 +801,32 @@ class Simulation:
         if rc:
             raise RuntimeError(f"pft_solver_download failed ({rc})")
 
+    # -- what the four reductions (f5, f6, f12, f13) share ---------------------------------------
+    def _gather_bytes(self, raw):
+        """every rank's `raw` (the same length on all of them) as a list of bytes in rank order
+        (collective: pft_comm_allgather_any makes the rounds); a single rank makes no collective"""
+        L_ = self.lib
+        comm = L_.pft_comm_current()
+        n = L_.pft_comm_size(comm) if comm else 1
+        if n == 1:
+            return [raw]
+        every = C.create_string_buffer(n * len(raw))
+        rc = L_.pft_comm_allgather_any(comm, raw, len(raw), every)
+        if rc:
+            raise RuntimeError(f"pft_comm_allgather failed ({rc})")
+        return [every.raw[r * len(raw):(r + 1) * len(raw)] for r in range(n)]
+
+    @staticmethod
+    def _answer(entry, where, make):
+        """make()'s answer for the entry `entry` after the check of `where`; RuntimeError when it is None
+        (where="device" and nothing resident: the solver's -3, the same on every rank)"""
+        _check_where(where)
+        d = make()
+        if d is None:
+            raise RuntimeError(f"{entry}: no state is resident on the device (no initialised solver, or no "
+                               "fused solve or device IC yet); solve first, or use where='host'")
+        return d
+
     # -- f5: diagnostics and the driver's snapshot loop ------------------------------------------
     def _diag_host_global(self, o, planes):
         """pft_diag_host of self.x, merged over the communicator's ranks in rank order (collective)"""
@@ -803,17 +835,10 @@ class Simulation:
         rc = L_.pft_diag_host(C.byref(self.grid), _dp(self.x), C.byref(o), C.byref(mine), planes)
         if rc:
             raise RuntimeError(f"pft_diag_host failed ({rc})")
-        comm = L_.pft_comm_current()
-        n = L_.pft_comm_size(comm) if comm else 1
-        if n == 1:
-            return mine, mine
-        every = (pft_diag * n)()
-        rc = L_.pft_comm_allgather(comm, C.byref(mine), C.sizeof(pft_diag), every)
-        if rc:
-            raise RuntimeError(f"pft_comm_allgather failed ({rc})")
-        glob = pft_diag.from_buffer_copy(every[0])
-        for r in range(1, n):
-            L_.pft_diag_combine(C.byref(glob), C.byref(every[r]))
+        parts = self._gather_bytes(bytes(mine))
+        glob = pft_diag.from_buffer_copy(parts[0])
+        for part in parts[1:]:
+            L_.pft_diag_combine(C.byref(glob), C.byref(pft_diag.from_buffer_copy(part)))
         return glob, mine
 
     def diagnostics(self, p_thr=0.5, gl_thr=0.5, where="device", per_plane=False):
@@ -824,13 +849,7 @@ class Simulation:
         IC).  where="host": pft_diag_host of self.x, merged over the ranks (collective too).
         per_plane: also ice_per_plane (this rank's planes) and first_row, and "local", this
         slab's own record."""
-        if where not in ("device", "host"):
-            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
-        d = self._diagnostics(p_thr, gl_thr, where, per_plane)
-        if d is None:
-            raise RuntimeError("diagnostics: no state is resident on the device (no initialised solver, or no "
-                               "fused solve or device IC yet); solve first, or use where='host'")
-        return d
+        return self._answer("diagnostics", where, lambda: self._diagnostics(p_thr, gl_thr, where, per_plane))
 
     def _diagnostics(self, p_thr, gl_thr, where, per_plane):
         """diagnostics(); None when where="device" and nothing is resident (pft_solver_diag's -3,
@@ -855,30 +874,16 @@ class Simulation:
 
     # -- f6: exact means and z-profiles ----------------------------------------------------------
     def _means_host_global(self, o, planes):
-        """pft_means_host of self.x, merged over the communicator's ranks in rank order (collective;
-        the record travels in pft_comm_allgather rounds of at most 256 bytes)"""
+        """pft_means_host of self.x, merged over the communicator's ranks in rank order (collective)"""
         L_ = self.lib
         mine = pft_means()
         rc = L_.pft_means_host(C.byref(self.grid), _dp(self.x), C.byref(o), C.byref(mine), planes)
         if rc:
             raise RuntimeError(f"pft_means_host failed ({rc})")
-        comm = L_.pft_comm_current()
-        n = L_.pft_comm_size(comm) if comm else 1
-        if n == 1:
-            return mine, mine
-        raw, size = bytes(mine), C.sizeof(pft_means)
-        parts = [bytearray() for _ in range(n)]
-        for off in range(0, size, 256):
-            piece = raw[off:off + 256]
-            every = C.create_string_buffer(n * len(piece))
-            rc = L_.pft_comm_allgather(comm, piece, len(piece), every)
-            if rc:
-                raise RuntimeError(f"pft_comm_allgather failed ({rc})")
-            for r in range(n):
-                parts[r] += every.raw[r * len(piece):(r + 1) * len(piece)]
-        glob = pft_means.from_buffer_copy(bytes(parts[0]))
-        for r in range(1, n):
-            L_.pft_means_combine(C.byref(glob), C.byref(pft_means.from_buffer_copy(bytes(parts[r]))))
+        parts = self._gather_bytes(bytes(mine))
+        glob = pft_means.from_buffer_copy(parts[0])
+        for part in parts[1:]:
+            L_.pft_means_combine(C.byref(glob), C.byref(pft_means.from_buffer_copy(part)))
         return glob, mine
 
     def means(self, p_thr=0.5, gl_thr=0.5, where="device", per_plane=False):
@@ -892,13 +897,7 @@ class Simulation:
         ice_u_profile and pore_p_profile, the means of each of this rank's planes (global rows
         first_row + k), first_row, "local", this slab's own scalars, and "record" /
         "plane_records", the raw pft_means structs."""
-        if where not in ("device", "host"):
-            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
-        d = self._means(p_thr, gl_thr, where, per_plane)
-        if d is None:
-            raise RuntimeError("means: no state is resident on the device (no initialised solver, or no "
-                               "fused solve or device IC yet); solve first, or use where='host'")
-        return d
+        return self._answer("means", where, lambda: self._means(p_thr, gl_thr, where, per_plane))
 
     def _means(self, p_thr, gl_thr, where, per_plane):
         """means(); None when where="device" and nothing is resident (pft_solver_means' -3, the
@@ -926,8 +925,7 @@ class Simulation:
 
     # -- f12: formula diagnostics ------------------------------------------------------------------
     def _formulas_host_global(self, progs, planes):
-        """pft_formula_host of self.x, merged over the communicator's ranks in rank order (collective;
-        the records travel in pft_comm_allgather rounds of at most 256 bytes)"""
+        """pft_formula_host of self.x, merged over the communicator's ranks in rank order (collective)"""
         L_ = self.lib
         names, lens, ops, args = progs
         nprog = len(names)
@@ -935,23 +933,10 @@ class Simulation:
         rc = L_.pft_formula_host(C.byref(self.grid), _dp(self.x), nprog, _ip(lens), _ip(ops), _dp(args), mine, planes)
         if rc:
             raise RuntimeError(f"pft_formula_host failed ({rc})")
-        comm = L_.pft_comm_current()
-        n = L_.pft_comm_size(comm) if comm else 1
-        if n == 1:
-            return mine, mine
-        raw, size = bytes(mine), C.sizeof(mine)
-        parts = [bytearray() for _ in range(n)]
-        for off in range(0, size, 256):
-            piece = raw[off:off + 256]
-            every = C.create_string_buffer(n * len(piece))
-            rc = L_.pft_comm_allgather(comm, piece, len(piece), every)
-            if rc:
-                raise RuntimeError(f"pft_comm_allgather failed ({rc})")
-            for r in range(n):
-                parts[r] += every.raw[r * len(piece):(r + 1) * len(piece)]
-        glob = (pft_fdiag * nprog).from_buffer_copy(bytes(parts[0]))
-        for r in range(1, n):
-            other = (pft_fdiag * nprog).from_buffer_copy(bytes(parts[r]))
+        parts = self._gather_bytes(bytes(mine))
+        glob = (pft_fdiag * nprog).from_buffer_copy(parts[0])
+        for part in parts[1:]:
+            other = (pft_fdiag * nprog).from_buffer_copy(part)
             for f in range(nprog):
                 L_.pft_fdiag_combine(C.byref(glob[f]), C.byref(other[f]))
         return glob, mine
@@ -971,14 +956,8 @@ class Simulation:
         first_row, "local", this slab's own scalars, and "record" / "plane_records", the raw
         pft_fdiag structs.  ValueError (frontend.EvalError is one) before any work for an undefined
         symbol, an empty dict, more than 8 formulas or programs of more than 256 entries."""
-        if where not in ("device", "host"):
-            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
-        progs = formula_programs(formulas, variables)
-        d = self._formulas(progs, where, per_plane)
-        if d is None:
-            raise RuntimeError("formulas: no state is resident on the device (no initialised solver, or no "
-                               "fused solve or device IC yet); solve first, or use where='host'")
-        return d
+        return self._answer("formulas", where,
+                            lambda: self._formulas(formula_programs(formulas, variables), where, per_plane))
 
     def _formula_not_exact(self, progs):
         """the name of the first formula that does not compile for the device, or None"""
@@ -1030,8 +1009,7 @@ class Simulation:
 
     # -- f13: histograms of formula values -----------------------------------------------------------
     def _hist_host_global(self, spec, plane_heads, plane_counts):
-        """pft_hist_host of self.x, merged over the communicator's ranks in rank order (collective;
-        the record travels in pft_comm_allgather rounds of at most 256 bytes)"""
+        """pft_hist_host of self.x, merged over the communicator's ranks in rank order (collective)"""
         L_ = self.lib
         edges = spec["edges"]
         nbins = edges.size - 1
@@ -1046,26 +1024,13 @@ class Simulation:
                               counts, plane_heads, plane_counts)
         if rc:
             raise RuntimeError(f"pft_hist_host failed ({rc})")
-        comm = L_.pft_comm_current()
-        n = L_.pft_comm_size(comm) if comm else 1
-        if n == 1:
-            return (head, counts), (head, counts)
-        raw = bytes(head) + bytes(counts)
-        parts = [bytearray() for _ in range(n)]
-        for off in range(0, len(raw), 256):
-            piece = raw[off:off + 256]
-            every = C.create_string_buffer(n * len(piece))
-            rc = L_.pft_comm_allgather(comm, piece, len(piece), every)
-            if rc:
-                raise RuntimeError(f"pft_comm_allgather failed ({rc})")
-            for r in range(n):
-                parts[r] += every.raw[r * len(piece):(r + 1) * len(piece)]
+        parts = self._gather_bytes(bytes(head) + bytes(counts))
         hs = C.sizeof(pft_hist_head)
-        ghead = pft_hist_head.from_buffer_copy(bytes(parts[0][:hs]))
-        gcounts = (C.c_longlong * nbins).from_buffer_copy(bytes(parts[0][hs:]))
-        for r in range(1, n):
-            oh = pft_hist_head.from_buffer_copy(bytes(parts[r][:hs]))
-            oc = (C.c_longlong * nbins).from_buffer_copy(bytes(parts[r][hs:]))
+        ghead = pft_hist_head.from_buffer_copy(parts[0][:hs])
+        gcounts = (C.c_longlong * nbins).from_buffer_copy(parts[0][hs:])
+        for part in parts[1:]:
+            oh = pft_hist_head.from_buffer_copy(part[:hs])
+            oc = (C.c_longlong * nbins).from_buffer_copy(part[hs:])
             L_.pft_hist_combine(nbins, C.byref(ghead), gcounts, C.byref(oh), oc)
         return (ghead, gcounts), (head, counts)
 
@@ -1084,14 +1049,8 @@ class Simulation:
         over_per_plane, nan_per_plane, selected_per_plane (this rank's planes, global rows first_row
         + k), first_row and "local", this slab's own dict.  ValueError before any work for bad
         edges, an undefined symbol or a syntax error."""
-        if where not in ("device", "host"):
-            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
-        spec = hist_spec(formula, bins, range, mask, variables)
-        d = self._histogram(spec, where, per_plane)
-        if d is None:
-            raise RuntimeError("histogram: no state is resident on the device (no initialised solver, or no "
-                               "fused solve or device IC yet); solve first, or use where='host'")
-        return d
+        return self._answer("histogram", where,
+                            lambda: self._histogram(hist_spec(formula, bins, range, mask, variables), where, per_plane))
 
     def _hist_not_exact(self, spec):
         """the text of the formula or mask that does not compile for the device, or None"""
@@ -1171,8 +1130,7 @@ class Simulation:
         region()).  where="device": gathered on the device from the resident state
         (pft_solver_region: the region image through pinned memory, no file, no download of the
         rest); RuntimeError when nothing is resident.  where="host": the same from self.x."""
-        if where not in ("device", "host"):
-            raise ValueError(f"where must be 'device' or 'host', not {where!r}")
+        _check_where(where)
         r = self._region(sel)
         _, kcount, klocal = self.region_share(r)
         out = np.zeros((3, kcount, r.count[1], r.count[0]))
@@ -1364,6 +1322,19 @@ class Simulation:
     def _run_series(self, targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
                     snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full, progs=None,
                     hists=None):
+        not_resident = ("run_series: no state is resident on the device after the solve "
+                        "(the host-staged path keeps none)")
+
+        def resident(call, *args):
+            """the device's answer; at the first snapshot of a host IC, whose state is still the host
+            array, the host's"""
+            d = call(*args, "device", False)
+            if d is None and s == first:
+                d = call(*args, "host", False)
+            if d is None:
+                raise RuntimeError(not_resident)
+            return d
+
         rows = []
         for s, T in enumerate(targets, first):
             rc = None
@@ -1372,38 +1343,14 @@ class Simulation:
             row = {"snapshot": s, "t": self.system.t, "h": self.system.h, "steps": self.system.steps,
                    "steps_total": self.system.steps_total, "rc": rc}
             if diag:
-                d = self._diagnostics(p_thr, gl_thr, "device", False)
-                if d is None and s == first:
-                    # the first snapshot of a host IC: the state is still the host array
-                    d = self._diagnostics(p_thr, gl_thr, "host", False)
-                if d is None:
-                    raise RuntimeError("run_series: no state is resident on the device after the solve "
-                                       "(the host-staged path keeps none)")
-                row.update(d)
+                row.update(resident(self._diagnostics, p_thr, gl_thr))
             if means:
-                d = self._means(p_thr, gl_thr, "device", False)
-                if d is None and s == first:
-                    d = self._means(p_thr, gl_thr, "host", False)
-                if d is None:
-                    raise RuntimeError("run_series: no state is resident on the device after the solve "
-                                       "(the host-staged path keeps none)")
-                row.update(d)
+                row.update(resident(self._means, p_thr, gl_thr))
             if progs is not None:
-                d = self._formulas(progs, "device", False)
-                if d is None and s == first:
-                    d = self._formulas(progs, "host", False)
-                if d is None:
-                    raise RuntimeError("run_series: no state is resident on the device after the solve "
-                                       "(the host-staged path keeps none)")
-                for name, rec in d.items():
+                for name, rec in resident(self._formulas, progs).items():
                     row.update({name + "_" + k: rec[k] for k in FORMULA_ROW_KEYS})
             for name, sp in (hists or {}).items():
-                d = self._histogram(sp, "device", False)
-                if d is None and s == first:
-                    d = self._histogram(sp, "host", False)
-                if d is None:
-                    raise RuntimeError("run_series: no state is resident on the device after the solve "
-                                       "(the host-staged path keeps none)")
+                d = resident(self._histogram, sp)
                 row[name] = d["counts"]
                 row.update({name + "_" + k: d[k] for k in HIST_ROW_KEYS})
             if snapshot_path is not None and not (s == first and skip_first):
@@ -1418,8 +1365,7 @@ class Simulation:
                     if snapshot_where == "device":
                         written = self._snapshot_device(name, info, PFT_SNAP_ASYNC if snapshot_async else 0, reg)
                         if not written and s != first:
-                            raise RuntimeError("run_series: no state is resident on the device after the solve "
-                                               "(the host-staged path keeps none)")
+                            raise RuntimeError(not_resident)
                     if not written:
                         # the host path; with "device" the first snapshot of a host IC, not yet resident
                         if not downloaded:

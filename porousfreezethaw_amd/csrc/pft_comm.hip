@@ -824,6 +824,23 @@ int pft_comm_allgather(pft_comm* c, const void* mine, int bytes, void* all)
   return 0;
 }
 
+int pft_comm_allgather_any(pft_comm* c, const void* mine, size_t bytes, void* all)
+{
+  // the one place that cuts a long message into pft_comm_allgather rounds: the first 256 bytes, the
+  // next 256, ..., a short last round.  (Loopback ranks are threads of one process: nothing static.)
+  enum { ROUND_BYTES = 256 };  // what one pft_comm_allgather carries
+  const int size = pft_comm_size(c);
+  char piece[PFT_IPC_MAX * ROUND_BYTES];
+  if (!mine || bytes < 1 || size > PFT_IPC_MAX) return -2;
+  for (size_t off = 0; off < bytes; off += ROUND_BYTES) {
+    const int n = (int)(bytes - off < ROUND_BYTES ? bytes - off : ROUND_BYTES);
+    const int rc = pft_comm_allgather(c, (const char*)mine + off, n, piece);
+    if (rc) return rc;
+    for (int q = 0; q < size && all; ++q) memcpy((char*)all + (size_t)q * bytes + off, piece + (size_t)q * n, n);
+  }
+  return 0;
+}
+
 int pft_comm_allreduce_max_i64(pft_comm* c, long long* v)
 {
   if (!c || c->size == 1) return 0;

@@ -230,6 +230,34 @@ __global__ __launch_bounds__(PFT_DBLOCK) void diag_kernel(const double* __restri
   }
 }
 
+// interior planes 1..n3 of u in buffer buf, one contiguous run (p and gl follow at s->fs and 2 s->fs;
+// the ghost planes 0, n3+1 and the far planes are never read); *head = 1 when the run starts on an
+// odd multiple of 8 bytes (the field stride is even: the same for u, p, gl)
+static const double* slab_fields(const pft_slab* s, int buf, int* head)
+{
+  const double* fu = s->buf[buf] + s->plane;
+  *head = (int)(((uintptr_t)fu >> 3) & 1);
+  return fu;
+}
+
+// The cut of the slab's planes into work items (f6, f12, f13): at most `cap` workgroups (8 per CU),
+// each inside one plane: a plane is cut into as many segments as the cap allows, each a whole number
+// of workgroup iterations; with fewer workgroups than planes a workgroup takes several planes in
+// turn.  An item is segment j of plane k, item = k * segs + j.
+static void plane_work_cut(const pft_slab* s, int* segs, int* seg_len, unsigned* wgs)
+{
+  const long plane = s->plane, n3 = s->d.n3;
+  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
+  const long wg_elems = 2L * PFT_DIAG_WG_PAIRS;
+  long want = cap / n3;
+  if (want < 1) want = 1;
+  const long len = ((plane + want - 1) / want + wg_elems - 1) / wg_elems * wg_elems;
+  const long items = (plane + len - 1) / len * n3;
+  *segs = (int)((plane + len - 1) / len);
+  *seg_len = (int)len;
+  *wgs = (unsigned)(items < cap ? items : cap);
+}
+
 extern "C" {
 
 int pft_slab_diag(pft_slab* s, int buf, const pft_diag_opts* opts, pft_diag* out, long long* ice_per_plane)
@@ -240,9 +268,8 @@ int pft_slab_diag(pft_slab* s, int buf, const pft_diag_opts* opts, pft_diag* out
   const size_t bytes = sizeof(unsigned long long) * (size_t)(PFT_DIAG_HEAD + s->d.n3);
   if (!s->diag_dev) HIPCHK(hipMalloc((void**)&s->diag_dev, bytes));
   if (!s->diag_host) HIPCHK(hipHostMalloc((void**)&s->diag_host, bytes, hipHostMallocDefault));
-  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
-  const double* fu = s->buf[buf] + plane;
-  const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
+  int head;
+  const double* fu = slab_fields(s, buf, &head);
   const long nq = (n + head + 1) / 2;
   if (plane > (1L << 30)) return -2;   // (the kernel's 32-bit plane bounds)
   // at most `cap` workgroups (all resident at once: 8 per CU), each a whole number of iterations
@@ -283,23 +310,9 @@ int pft_slab_diag(pft_slab* s, int buf, const pft_diag_opts* opts, pft_diag* out
   return 0;
 }
 
-int pft_slab_diag_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_diag[i]) HIPCHK(hipEventCreate(&s->ev_diag[i]));
-  s->diag_timing = on ? 1 : 0;
-  return 0;
-}
+int pft_slab_diag_timing(pft_slab* s, int on) { return slab_timing_set(s, &pft_slab::diag_timing, &pft_slab::ev_diag, on); }
 
-int pft_slab_diag_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->diag_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_diag[0], s->ev_diag[1]));
-  *ms = f;
-  return 0;
-}
+int pft_slab_diag_last_ms(pft_slab* s, double* ms) { return slab_timing_ms(s, &pft_slab::diag_timing, &pft_slab::ev_diag, ms); }
 
 }  // extern "C"
 
@@ -472,6 +485,29 @@ __device__ __forceinline__ void means_accumulate(MeansPair& st, const double (&x
   }
 }
 
+// A work item (f6, f12, f13: segment j of interior plane k, item = k * segs + j) and its pair-aligned
+// frame: elements r = 0 .. span - 1 stand for e_base + r of the run of n3 planes, e_base on a 16-byte
+// boundary at or one below the item's first element; of them [r_lo, r_hi) are the item's (nothing
+// else is read), element r_lo being element `first` of the plane
+struct ItemFrame {
+  long e_base;
+  int k, first, r_lo, r_hi, span;
+};
+
+__device__ __forceinline__ ItemFrame item_frame(long item, int segs, int seg_len, int plane, int head)
+{
+  ItemFrame f;
+  f.k = (int)(item / segs);
+  const int j = (int)(item - (long)f.k * segs);
+  f.first = j * seg_len;                                            // within the plane
+  const int len = plane - f.first < seg_len ? plane - f.first : seg_len;
+  const long a = (long)f.k * plane + f.first;                       // within the run of n3 planes
+  f.e_base = 2 * ((a + head) >> 1) - head;
+  f.r_lo = (int)(a - f.e_base), f.r_hi = f.r_lo + len;
+  f.span = (f.r_hi + 1) & ~1;
+  return f;
+}
+
 struct MeansState {
   MeansPair u, p;
   unsigned long long n_u, n_p, n_ui, n_pp;   // wave-uniform counts
@@ -543,18 +579,11 @@ __global__ __launch_bounds__(PFT_DBLOCK) void means_kernel(const double* __restr
   st.p.cur = 31;
   const long items = (long)n3 * segs;
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    const int k = (int)(item / segs), j = (int)(item - (long)k * segs);
-    const int first = j * seg_len;                                    // within the plane
-    const int len = plane - first < seg_len ? plane - first : seg_len;
-    const long a = (long)k * plane + first;                           // within the run of n3 planes
-    // the frame: elements r = 0 .. span - 1 stand for e_base + r of the run, e_base on a 16-byte
-    // boundary at or one below a; of them [r_lo, r_hi) are the item's (nothing else is read)
-    const long e_base = 2 * ((a + head) >> 1) - head;
-    const int r_lo = (int)(a - e_base), r_hi = r_lo + len;
-    const int span = (r_hi + 1) & ~1;
-    const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
-    const double* wp = fp + e_base;
-    const double* wg = fg + e_base;
+    const ItemFrame it = item_frame(item, segs, seg_len, plane, head);
+    const int k = it.k, r_lo = it.r_lo, r_hi = it.r_hi, span = it.span;
+    const double* wu = fu + it.e_base;   // (e_base = -1: one before the run, never read at r = 0)
+    const double* wp = fp + it.e_base;
+    const double* wg = fg + it.e_base;
     st.n_u = st.n_p = st.n_ui = st.n_pp = 0;
     for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
       if (r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi)
@@ -612,26 +641,16 @@ int pft_slab_means(pft_slab* s, int buf, const pft_diag_opts* opts, pft_means* t
   const size_t bytes = sizeof(pft_means) * ((size_t)s->d.n3 + 1);
   if (!s->means_dev) HIPCHK(hipMalloc((void**)&s->means_dev, bytes));
   if (!s->means_host) HIPCHK(hipHostMalloc((void**)&s->means_host, bytes, hipHostMallocDefault));
-  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
-  const double* fu = s->buf[buf] + plane;
-  const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
-  // at most `cap` workgroups (8 per CU), each inside one plane: a plane is cut into as many
-  // segments as the cap allows, each a whole number of workgroup iterations; with fewer workgroups
-  // than planes a workgroup takes several planes in turn
-  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
-  const long wg_elems = 2L * PFT_DIAG_WG_PAIRS;
-  long want = cap / s->d.n3;
-  if (want < 1) want = 1;
-  const long seg_len = ((plane + want - 1) / want + wg_elems - 1) / wg_elems * wg_elems;
-  const long segs = (plane + seg_len - 1) / seg_len;
-  const long items = segs * s->d.n3;
-  const long wgs = items < cap ? items : cap;
+  int head, segs, seg_len;
+  unsigned wgs;
+  const double* fu = slab_fields(s, buf, &head);
+  plane_work_cut(s, &segs, &seg_len, &wgs);
   const double p_thr = opts ? opts->p_thr : 0.5, gl_thr = opts ? opts->gl_thr : 0.5;
   // no state carries over between calls: every accumulator word is zeroed on the stream first
   HIPCHK(hipMemsetAsync(s->means_dev, 0, bytes, s->stream));
   if (s->means_timing) HIPCHK(hipEventRecord(s->ev_means[0], s->stream));
-  means_kernel<<<(unsigned)wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head, s->d.n3,
-                                                            (int)segs, (int)seg_len, p_thr, gl_thr, s->means_dev);
+  means_kernel<<<wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head, s->d.n3, segs, seg_len,
+                                                  p_thr, gl_thr, s->means_dev);
   HIPCHK(hipGetLastError());
   means_total_kernel<<<(PFT_MEANS_REC + 63) / 64, 256, 0, s->stream>>>(s->means_dev, s->d.n3);
   HIPCHK(hipGetLastError());
@@ -645,23 +664,9 @@ int pft_slab_means(pft_slab* s, int buf, const pft_diag_opts* opts, pft_means* t
   return 0;
 }
 
-int pft_slab_means_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_means[i]) HIPCHK(hipEventCreate(&s->ev_means[i]));
-  s->means_timing = on ? 1 : 0;
-  return 0;
-}
+int pft_slab_means_timing(pft_slab* s, int on) { return slab_timing_set(s, &pft_slab::means_timing, &pft_slab::ev_means, on); }
 
-int pft_slab_means_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->means_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_means[0], s->ev_means[1]));
-  *ms = f;
-  return 0;
-}
+int pft_slab_means_last_ms(pft_slab* s, double* ms) { return slab_timing_ms(s, &pft_slab::means_timing, &pft_slab::ev_means, ms); }
 
 }  // extern "C"
 
@@ -736,6 +741,38 @@ __device__ __forceinline__ double formula_eval(const FormulaProgs& P, int c0, in
   return err ? 0.0 : top;   // a math error anywhere yields 0, as the reference's Eval()
 }
 
+// the pair of elements r, r + 1 of the fields that `need` names (the others stay 0): one 16-byte load
+// per field where both belong to the item (full), else each element alone under its own test
+__device__ __forceinline__ void formula_load(bool full, int need, const double* __restrict__ fu,
+                                             const double* __restrict__ fp, const double* __restrict__ fg, int r, int r_lo,
+                                             int r_hi, double (&u)[2], double (&p)[2], double (&g)[2], bool (&v)[2])
+{
+  if (full) {
+    if (need & FM_NEED_U) {
+      const double2 a = *reinterpret_cast<const double2*>(fu + r);
+      u[0] = a.x, u[1] = a.y;
+    }
+    if (need & FM_NEED_P) {
+      const double2 a = *reinterpret_cast<const double2*>(fp + r);
+      p[0] = a.x, p[1] = a.y;
+    }
+    if (need & FM_NEED_GL) {
+      const double2 a = *reinterpret_cast<const double2*>(fg + r);
+      g[0] = a.x, g[1] = a.y;
+    }
+    v[0] = v[1] = true;
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool ok = r + h >= r_lo && r + h < r_hi;
+      v[h] = ok;
+      if (ok && (need & FM_NEED_U)) u[h] = fu[r + h];
+      if (ok && (need & FM_NEED_P)) p[h] = fp[r + h];
+      if (ok && (need & FM_NEED_GL)) g[h] = fg[r + h];
+    }
+  }
+}
+
 struct FormulaState {
   MeansPair sum;
   unsigned long long n, nonzero, nonfinite;   // wave-uniform counts
@@ -755,30 +792,7 @@ __device__ __forceinline__ void formula_iter(FormulaState& st, const FormulaProg
     const int r = r0 + 128 * jj + 2 * lane;
     double u[2] = {0.0, 0.0}, p[2] = {0.0, 0.0}, g[2] = {0.0, 0.0}, x[2];
     bool v[2];
-    if (FULL) {
-      if (need & FM_NEED_U) {
-        const double2 a = *reinterpret_cast<const double2*>(fu + r);
-        u[0] = a.x, u[1] = a.y;
-      }
-      if (need & FM_NEED_P) {
-        const double2 a = *reinterpret_cast<const double2*>(fp + r);
-        p[0] = a.x, p[1] = a.y;
-      }
-      if (need & FM_NEED_GL) {
-        const double2 a = *reinterpret_cast<const double2*>(fg + r);
-        g[0] = a.x, g[1] = a.y;
-      }
-      v[0] = v[1] = true;
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool ok = r + h >= r_lo && r + h < r_hi;
-        v[h] = ok;
-        if (ok && (need & FM_NEED_U)) u[h] = fu[r + h];
-        if (ok && (need & FM_NEED_P)) p[h] = fp[r + h];
-        if (ok && (need & FM_NEED_GL)) g[h] = fg[r + h];
-      }
-    }
+    formula_load(FULL, need, fu, fp, fg, r, r_lo, r_hi, u, p, g, v);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       // the node's place in its plane; a slot outside the item evaluates node 0 (inside every
@@ -827,17 +841,11 @@ __global__ __launch_bounds__(PFT_DBLOCK) void formula_kernel(const double* __res
   unsigned long long* planes = rec + (size_t)(PFT_FORMULA_MAX + (size_t)f * n3) * FD_REC;
   const long items = (long)n3 * segs;
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    const int k = (int)(item / segs), j = (int)(item - (long)k * segs);
-    const int first = j * seg_len;                                    // within the plane
-    const int len = plane - first < seg_len ? plane - first : seg_len;
-    const long a = (long)k * plane + first;                           // within the run of n3 planes
-    // the frame of means_kernel: e_base on a 16-byte boundary at or one below a
-    const long e_base = 2 * ((a + head) >> 1) - head;
-    const int r_lo = (int)(a - e_base), r_hi = r_lo + len;
-    const int span = (r_hi + 1) & ~1;
-    const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
-    const double* wp = fp + e_base;
-    const double* wg = fg + e_base;
+    const ItemFrame it = item_frame(item, segs, seg_len, plane, head);
+    const int k = it.k, first = it.first, r_lo = it.r_lo, r_hi = it.r_hi, span = it.span;
+    const double* wu = fu + it.e_base;   // (e_base = -1: one before the run, never read at r = 0)
+    const double* wp = fp + it.e_base;
+    const double* wg = fg + it.e_base;
     st.n = st.nonzero = st.nonfinite = 0;
     st.kmax = st.kmin = st.kabs = 0;
     for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
@@ -1054,25 +1062,17 @@ int pft_slab_formulas(pft_slab* s, int buf, int nprog, const pft_ic_prog* progs,
   const size_t words = (size_t)FD_REC * (PFT_FORMULA_MAX + (size_t)PFT_FORMULA_MAX * n3);
   if (!s->formula_dev) HIPCHK(hipMalloc((void**)&s->formula_dev, sizeof(unsigned long long) * words));
   if (!s->formula_host) HIPCHK(hipHostMalloc((void**)&s->formula_host, sizeof(unsigned long long) * words, hipHostMallocDefault));
-  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
-  const double* fu = s->buf[buf] + plane;
-  const int head = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
-  // pft_slab_means' cut of the planes into work items; the cap holds per program
-  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
-  const long wg_elems = 2L * PFT_DIAG_WG_PAIRS;
-  long want = cap / n3;
-  if (want < 1) want = 1;
-  const long seg_len = ((plane + want - 1) / want + wg_elems - 1) / wg_elems * wg_elems;
-  const long segs = (plane + seg_len - 1) / seg_len;
-  const long items = segs * n3;
-  const long wgs = items < cap ? items : cap;
+  int head, segs, seg_len;
+  unsigned wgs;   // (the cap holds per program)
+  const double* fu = slab_fields(s, buf, &head);
+  plane_work_cut(s, &segs, &seg_len, &wgs);
   const size_t used = sizeof(unsigned long long) * FD_REC * (PFT_FORMULA_MAX + (size_t)nprog * n3);
   HIPCHK(hipMemcpyAsync(s->formula_prog_dev, s->formula_prog_host, blob, hipMemcpyHostToDevice, s->stream));
   // no state carries over between calls: every accumulator word is zeroed on the stream first
   HIPCHK(hipMemsetAsync(s->formula_dev, 0, used, s->stream));
   if (s->formula_timing) HIPCHK(hipEventRecord(s->ev_formula[0], s->stream));
-  formula_kernel<<<dim3((unsigned)wgs, (unsigned)nprog), PFT_DBLOCK, 0, s->stream>>>(
-      fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head, s->d.n1, n3, (int)segs, (int)seg_len, P, s->formula_dev);
+  formula_kernel<<<dim3(wgs, (unsigned)nprog), PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head,
+                                                                           s->d.n1, n3, segs, seg_len, P, s->formula_dev);
   HIPCHK(hipGetLastError());
   formula_total_kernel<<<dim3((FD_REC + 63) / 64, (unsigned)nprog), 256, 0, s->stream>>>(s->formula_dev, n3);
   HIPCHK(hipGetLastError());
@@ -1091,23 +1091,9 @@ int pft_slab_formulas(pft_slab* s, int buf, int nprog, const pft_ic_prog* progs,
   return 0;
 }
 
-int pft_slab_formulas_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_formula[i]) HIPCHK(hipEventCreate(&s->ev_formula[i]));
-  s->formula_timing = on ? 1 : 0;
-  return 0;
-}
+int pft_slab_formulas_timing(pft_slab* s, int on) { return slab_timing_set(s, &pft_slab::formula_timing, &pft_slab::ev_formula, on); }
 
-int pft_slab_formulas_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->formula_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_formula[0], s->ev_formula[1]));
-  *ms = f;
-  return 0;
-}
+int pft_slab_formulas_last_ms(pft_slab* s, double* ms) { return slab_timing_ms(s, &pft_slab::formula_timing, &pft_slab::ev_formula, ms); }
 
 }  // extern "C"
 
@@ -1157,30 +1143,7 @@ __device__ __forceinline__ void hist_iter(HistState& st, const FormulaProgs& P, 
     const int r = r0 + 128 * jj + 2 * lane;
     double u[2] = {0.0, 0.0}, p[2] = {0.0, 0.0}, g[2] = {0.0, 0.0};
     bool v[2];
-    if (full) {
-      if (need & FM_NEED_U) {
-        const double2 a = *reinterpret_cast<const double2*>(fu + r);
-        u[0] = a.x, u[1] = a.y;
-      }
-      if (need & FM_NEED_P) {
-        const double2 a = *reinterpret_cast<const double2*>(fp + r);
-        p[0] = a.x, p[1] = a.y;
-      }
-      if (need & FM_NEED_GL) {
-        const double2 a = *reinterpret_cast<const double2*>(fg + r);
-        g[0] = a.x, g[1] = a.y;
-      }
-      v[0] = v[1] = true;
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool ok = r + h >= r_lo && r + h < r_hi;
-        v[h] = ok;
-        if (ok && (need & FM_NEED_U)) u[h] = fu[r + h];
-        if (ok && (need & FM_NEED_P)) p[h] = fp[r + h];
-        if (ok && (need & FM_NEED_GL)) g[h] = fg[r + h];
-      }
-    }
+    formula_load(full, need, fu, fp, fg, r, r_lo, r_hi, u, p, g, v);
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {
       const double uh = h ? u[1] : u[0], ph = h ? p[1] : p[0], gh = h ? g[1] : g[0];
@@ -1261,17 +1224,11 @@ __global__ __launch_bounds__(PFT_DBLOCK) void hist_kernel(const double* __restri
   double* stack = s_stack + threadIdx.x;
   const long items = (long)n3 * segs;
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    const int k = (int)(item / segs), j = (int)(item - (long)k * segs);
-    const int first = j * seg_len;                                    // within the plane
-    const int len = plane - first < seg_len ? plane - first : seg_len;
-    const long a = (long)k * plane + first;                           // within the run of n3 planes
-    // the frame of means_kernel: e_base on a 16-byte boundary at or one below a
-    const long e_base = 2 * ((a + head) >> 1) - head;
-    const int r_lo = (int)(a - e_base), r_hi = r_lo + len;
-    const int span = (r_hi + 1) & ~1;
-    const double* wu = fu + e_base;   // (e_base = -1: one before the run, never read at r = 0)
-    const double* wp = fp + e_base;
-    const double* wg = fg + e_base;
+    const ItemFrame it = item_frame(item, segs, seg_len, plane, head);
+    const int k = it.k, first = it.first, r_lo = it.r_lo, r_hi = it.r_hi, span = it.span;
+    const double* wu = fu + it.e_base;   // (e_base = -1: one before the run, never read at r = 0)
+    const double* wp = fp + it.e_base;
+    const double* wg = fg + it.e_base;
     st.selected = st.nan = st.under = st.over = 0;
     for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
       hist_iter(st, P, c0, c1, m0, m1, need, r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi, wu, wp, wg, r0, r_lo, r_hi,
@@ -1369,25 +1326,17 @@ int pft_slab_hist(pft_slab* s, int buf, const pft_ic_prog* value_prog, const pft
   }
   int trips = 0;   // ceil(log2(nbins + 1)): the first power of two that is >= the number of edges
   while ((1 << trips) < nbins + 1) ++trips;
-  // interior planes 1..n3 of each field; the ghost planes 0, n3+1 and the far planes are never read
-  const double* fu = s->buf[buf] + plane;
-  const int head_odd = (int)(((uintptr_t)fu >> 3) & 1);   // (the field stride is even: the same for u, p, gl)
-  // pft_slab_means' cut of the planes into work items
-  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
-  const long wg_elems = 2L * PFT_DIAG_WG_PAIRS;
-  long want = cap / n3;
-  if (want < 1) want = 1;
-  const long seg_len = ((plane + want - 1) / want + wg_elems - 1) / wg_elems * wg_elems;
-  const long segs = (plane + seg_len - 1) / seg_len;
-  const long items = segs * n3;
-  const long wgs = items < cap ? items : cap;
+  int head_odd, segs, seg_len;
+  unsigned wgs;
+  const double* fu = slab_fields(s, buf, &head_odd);
+  plane_work_cut(s, &segs, &seg_len, &wgs);
   HIPCHK(hipMemcpyAsync(s->formula_prog_dev, s->formula_prog_host, blob, hipMemcpyHostToDevice, s->stream));
   // no state carries over between calls: every accumulator word is zeroed on the stream first
   HIPCHK(hipMemsetAsync(s->hist_dev, 0, bytes, s->stream));
   if (s->hist_timing) HIPCHK(hipEventRecord(s->ev_hist[0], s->stream));
-  hist_kernel<<<(unsigned)wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head_odd, s->d.n1, n3,
-                                                           (int)segs, (int)seg_len, P, mask_prog ? 1 : 0,
-                                                           (const double*)edges_dev, nbins, trips, s->hist_dev);
+  hist_kernel<<<wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fu + s->fs, fu + 2 * s->fs, (int)plane, head_odd, s->d.n1, n3, segs,
+                                                 seg_len, P, mask_prog ? 1 : 0, (const double*)edges_dev, nbins, trips,
+                                                 s->hist_dev);
   HIPCHK(hipGetLastError());
   hist_total_kernel<<<(row + 63) / 64, 256, 0, s->stream>>>(s->hist_dev, n3, row);
   HIPCHK(hipGetLastError());
@@ -1405,22 +1354,8 @@ int pft_slab_hist(pft_slab* s, int buf, const pft_ic_prog* value_prog, const pft
   return 0;
 }
 
-int pft_slab_hist_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_hist[i]) HIPCHK(hipEventCreate(&s->ev_hist[i]));
-  s->hist_timing = on ? 1 : 0;
-  return 0;
-}
+int pft_slab_hist_timing(pft_slab* s, int on) { return slab_timing_set(s, &pft_slab::hist_timing, &pft_slab::ev_hist, on); }
 
-int pft_slab_hist_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->hist_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_hist[0], s->ev_hist[1]));
-  *ms = f;
-  return 0;
-}
+int pft_slab_hist_last_ms(pft_slab* s, double* ms) { return slab_timing_ms(s, &pft_slab::hist_timing, &pft_slab::ev_hist, ms); }
 
 }  // extern "C"

@@ -252,6 +252,27 @@ PFT_LOCAL int slab_wait(pft_slab* s, hipEvent_t ev, const char* what);
 // The runtime (stage, calc_mode, flag) to template arguments: f is a generic lambda, called with the
 // value as a std::integral_constant, so each call site names its kernel once and the compiler
 // instantiates it for every value (no table, no indirect call).  The callers checked the value.
+// HIP events around a family's kernels (diag, means, formulas, hist, snapshot): its pft_slab_*_timing
+// entry switches them on (the events are made at the first use), its pft_slab_*_last_ms reads the
+// last call's time; flag and ev name the family's own fields
+static inline int slab_timing_set(pft_slab* s, int pft_slab::*flag, hipEvent_t (pft_slab::*ev)[2], int on)
+{
+  if (!s) return -2;
+  for (int i = 0; i < 2 && on; ++i)
+    if (!(s->*ev)[i]) HIPCHK(hipEventCreate(&(s->*ev)[i]));
+  s->*flag = on ? 1 : 0;
+  return 0;
+}
+
+static inline int slab_timing_ms(pft_slab* s, int pft_slab::*flag, hipEvent_t (pft_slab::*ev)[2], double* ms)
+{
+  if (!s || !ms || !(s->*flag)) return -2;
+  float f = 0.0f;
+  HIPCHK(hipEventElapsedTime(&f, (s->*ev)[0], (s->*ev)[1]));
+  *ms = f;
+  return 0;
+}
+
 template <int N>
 using pft_int = std::integral_constant<int, N>;
 

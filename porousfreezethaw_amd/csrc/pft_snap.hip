@@ -373,22 +373,8 @@ int pft_slab_region_export(pft_slab* s, int buf, const pft_region* r, int link, 
   return 0;
 }
 
-int pft_slab_snapshot_timing(pft_slab* s, int on)
-{
-  if (!s) return -2;
-  for (int i = 0; i < 2 && on; ++i)
-    if (!s->ev_snap[i]) HIPCHK(hipEventCreate(&s->ev_snap[i]));
-  s->snap_timing = on ? 1 : 0;
-  return 0;
-}
+int pft_slab_snapshot_timing(pft_slab* s, int on) { return slab_timing_set(s, &pft_slab::snap_timing, &pft_slab::ev_snap, on); }
 
-int pft_slab_snapshot_last_ms(pft_slab* s, double* ms)
-{
-  if (!s || !ms || !s->snap_timing) return -2;
-  float f = 0.0f;
-  HIPCHK(hipEventElapsedTime(&f, s->ev_snap[0], s->ev_snap[1]));
-  *ms = f;
-  return 0;
-}
+int pft_slab_snapshot_last_ms(pft_slab* s, double* ms) { return slab_timing_ms(s, &pft_slab::snap_timing, &pft_slab::ev_snap, ms); }
 
 }  // extern "C"

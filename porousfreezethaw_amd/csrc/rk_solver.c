@@ -711,103 +711,112 @@ int pft_solver_download(RK_MPI_S_SOLUTION * system)
 
 #define PFT_DIAG_MAX_RANKS 64   /* the ipc transport's limit (PFT_IPC_MAX) */
 
-int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * local, long long * ice_per_plane)
+/* the rule of every entry that reads the resident state: -3 with no initialised solver or no resident
+   state (before the first fused solve with a host IC, the host-staged path, after a failed call): no
+   stale numbers.  A collective entry is also -2 inside a Service_Callback with several ranks: only
+   one rank may ask there, another rank's callback need not */
+static int resident_state(int collective)
 {
-	/* f5: the diagnostics of the device-resident x.  Each rank reduces its slab; the records
-	   travel with the rank's status in one allgather and are merged in rank order, so every rank
-	   has the same record and returns the same code (a rank that failed locally still takes part,
-	   as in ic_device_finish) */
-	struct { long long status; pft_diag d; } mine, all[PFT_DIAG_MAX_RANKS];
+	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if(collective && R.in_callback && pft_comm_size(comm()) > 1) return -2;
+	return 0;
+}
+
+/* a compile outcome as a rank for a max over the ranks, and back: 1 (not device-exact) and -2 (a bad
+   program) are the same on every rank, -1 (out of memory) is local; -1 over -2 over 1 over 0 */
+static long long compile_rank(int rc)
+{
+	return rc == -1 ? 3 : (rc == -2 ? 2 : (rc == 1 ? 1 : (rc ? 3 : 0)));
+}
+
+static int compile_code(long long v)
+{
+	return v == 3 ? -1 : (v == 2 ? -2 : (v == 1 ? 1 : 0));
+}
+
+/* the ranks agree a compile outcome before anything else collective, so that every rank returns the
+   same code (a single rank keeps its own): 0, or the collective's error */
+static int compile_agree(int * rc)
+{
+	long long v = compile_rank(*rc);
+	int crc;
+	if(pft_comm_size(comm()) == 1) return 0;
+	if((crc = pft_comm_allreduce_max_i64(comm(), &v))) return crc;
+	*rc = compile_code(v);
+	return 0;
+}
+
+/* The gather of the four reductions (f5, f6, f12, f13).  `mine` is a {long long status; record}
+   message of `used` bytes; every rank sends it whatever its status (a rank that failed locally, or
+   whose allocation failed here -- it reports -1 -- still takes part, so that no other rank is left
+   inside a collective: pft_comm_allgather_any makes the rounds), and the statuses are judged after
+   the rounds.  0 with rank r's message at *all + r*used, to be given to drop_records; or
+   PFT_SOLVE_DEVICE_ERROR on every rank, with R.last_status the rank's own non-zero status, otherwise
+   the lowest-ranked bad rank's.  A single rank makes no collective and no allocation: *all is mine.
+   (Loopback ranks are threads of one process: nothing static.) */
+static int gather_records(long long status, void * mine, size_t used, char ** all)
+{
 	pft_comm * c = comm();
 	const int nprocs = pft_comm_size(c);
-	int rc, r, bad = 0;
+	int rc = 0, r;
+	*all = nprocs == 1 ? (char *)mine : (char *)malloc((size_t)nprocs * used);
+	if(!*all && !status) status = -1;
+	memcpy(mine, &status, sizeof status);
+	if(nprocs > 1 && (rc = pft_comm_allgather_any(c, mine, used, *all))) status = rc;
+	for(r = 0; r < nprocs && !status; r++) memcpy(&status, *all + (size_t)r*used, sizeof status);
+	if(status) {
+		if(*all != (char *)mine) free(*all);
+		R.last_status = (int)status;
+		return PFT_SOLVE_DEVICE_ERROR;
+	}
+	return 0;
+}
+
+static void drop_records(char * all, const void * mine)
+{
+	if(all != (const char *)mine) free(all);
+}
+
+int pft_solver_diag(const pft_diag_opts * opts, pft_diag * global, pft_diag * local, long long * ice_per_plane)
+{
+	/* f5: the diagnostics of the device-resident x.  Each rank reduces its slab; the records travel
+	   with the rank's status (gather_records: one round) and are merged in rank order, so every rank
+	   has the same record and returns the same code */
+	struct diag_msg { long long status; pft_diag d; } mine;
+	char * all;
+	const int nprocs = pft_comm_size(comm());
+	int rc, r;
 	if(!global) return -2;
-	/* no initialised solver, or no resident state (before the first fused solve with a host IC,
-	   the host-staged path, after a failed call): no stale numbers */
-	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
-	/* inside a Service_Callback only one rank may ask: another rank's callback need not */
-	if(R.in_callback && nprocs > 1) return -2;
+	if((rc = resident_state(1))) return rc;
 	if(nprocs > PFT_DIAG_MAX_RANKS || sizeof(mine) > 256) return -2;
 	memset(&mine, 0, sizeof mine);
 	rc = pft_slab_diag(R.slab, PFT_BUF_X, opts, &mine.d, ice_per_plane);
-	mine.status = rc;
-	if(nprocs == 1) {
-		if(rc) { R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
-		*global = mine.d;
-		if(local) *local = mine.d;
-		return 0;
-	}
-	if((rc = pft_comm_allgather(c, &mine, (int)sizeof mine, all))) {
-		R.last_status = rc;
-		return PFT_SOLVE_DEVICE_ERROR;
-	}
-	for(r = 0; r < nprocs; r++) if(all[r].status) bad = 1;
-	if(bad) {
-		R.last_status = mine.status ? (int)mine.status : (int)all[0].status;
-		for(r = 0; r < nprocs && !R.last_status; r++) R.last_status = (int)all[r].status;
-		return PFT_SOLVE_DEVICE_ERROR;
-	}
-	*global = all[0].d;
-	for(r = 1; r < nprocs; r++) pft_diag_combine(global, &all[r].d);
+	if((rc = gather_records(rc, &mine, sizeof mine, &all))) return rc;
+	*global = ((const struct diag_msg *)all)->d;
+	for(r = 1; r < nprocs; r++) pft_diag_combine(global, &((const struct diag_msg *)all)[r].d);
 	if(local) *local = mine.d;
+	drop_records(all, &mine);
 	return 0;
 }
 
 int pft_solver_means(const pft_diag_opts * opts, pft_means * global, pft_means * local, pft_means * per_plane)
 {
-	/* f6: the exact sums of the device-resident x, under pft_solver_diag's rules.  A rank's record
-	   and its status are longer than one allgather round carries, so they travel in rounds of at
-	   most 256 bytes; every rank makes every round (a rank that failed locally still takes part)
-	   and merges the records in rank order: integer sums, the same bits on every rank */
-	enum { ROUND = 256 };
-	struct means_msg { long long status; pft_means m; };
-	struct means_msg * all;      /* (loopback ranks are threads of one process: nothing static) */
-	char piece[PFT_DIAG_MAX_RANKS * ROUND];
-	struct means_msg mine;
-	pft_comm * c = comm();
-	const int nprocs = pft_comm_size(c);
-	int rc, r, bad = 0, first_bad = 0;
-	size_t off;
+	/* f6: the exact sums of the device-resident x, under pft_solver_diag's rules; the records are
+	   merged in rank order: integer sums, the same bits on every rank */
+	struct means_msg { long long status; pft_means m; } mine;
+	char * all;
+	const int nprocs = pft_comm_size(comm());
+	int rc, r;
 	if(!global) return -2;
-	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
-	if(R.in_callback && nprocs > 1) return -2;
+	if((rc = resident_state(1))) return rc;
 	if(nprocs > PFT_DIAG_MAX_RANKS) return -2;
 	memset(&mine, 0, sizeof mine);
 	rc = pft_slab_means(R.slab, PFT_BUF_X, opts, &mine.m, per_plane);
-	mine.status = rc;
-	if(nprocs == 1) {
-		if(rc) { R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
-		*global = mine.m;
-		if(local) *local = mine.m;
-		return 0;
-	}
-	/* (a failed allocation is this rank's failure, met after the rounds like any other) */
-	all = (struct means_msg *)malloc((size_t)nprocs * sizeof *all);
-	if(!all && !mine.status) mine.status = -1;
-	for(off = 0; off < sizeof mine; off += ROUND) {
-		const int bytes = (int)(sizeof mine - off < ROUND ? sizeof mine - off : ROUND);
-		if((rc = pft_comm_allgather(c, (const char *)&mine + off, bytes, piece))) {
-			free(all);
-			R.last_status = rc;
-			return PFT_SOLVE_DEVICE_ERROR;
-		}
-		if(off == 0)
-			for(r = 0; r < nprocs; r++) {
-				long long st;
-				memcpy(&st, piece + (size_t)r*bytes, sizeof st);
-				if(st) { bad = 1; if(!first_bad) first_bad = (int)st; }
-			}
-		for(r = 0; r < nprocs && all; r++) memcpy((char *)&all[r] + off, piece + (size_t)r*bytes, bytes);
-	}
-	if(bad) {
-		free(all);
-		R.last_status = mine.status ? (int)mine.status : first_bad;
-		return PFT_SOLVE_DEVICE_ERROR;
-	}
-	*global = all[0].m;
-	for(r = 1; r < nprocs; r++) pft_means_combine(global, &all[r].m);
+	if((rc = gather_records(rc, &mine, sizeof mine, &all))) return rc;
+	*global = ((const struct means_msg *)all)->m;
+	for(r = 1; r < nprocs; r++) pft_means_combine(global, &((const struct means_msg *)all)[r].m);
 	if(local) *local = mine.m;
-	free(all);
+	drop_records(all, &mine);
 	return 0;
 }
 
@@ -815,25 +824,18 @@ int pft_solver_formulas(int nprog, const int * lens, const int * ops, const doub
                         pft_fdiag * local, pft_fdiag * per_plane)
 {
 	/* f12: the formula diagnostics of the device-resident x, under pft_solver_diag's rules.  Every
-	   rank compiles first and the outcome is agreed before any device work, as in
-	   pft_solver_ic_formulas_device: 1 (not device-exact) and -2 (a bad program) are the same on every
-	   rank, -1 (out of memory) is local -- every rank returns the same code, -1 over -2 over 1.  Then
-	   each rank reduces its slab and the records travel with its status in rounds of at most 256
-	   bytes, as pft_solver_means' do; they are merged in rank order */
-	enum { ROUND = 256 };
-	struct formula_msg { long long status; pft_fdiag d[PFT_FORMULA_MAX]; };
-	struct formula_msg * all;    /* (loopback ranks are threads of one process: nothing static) */
-	char piece[PFT_DIAG_MAX_RANKS * ROUND];
-	struct formula_msg mine;
+	   rank compiles first and the outcome is agreed before any device work (compile_agree), as in
+	   pft_solver_ic_formulas_device.  Then each rank reduces its slab and the used part of its
+	   message travels (gather_records); the records are merged in rank order */
+	struct formula_msg { long long status; pft_fdiag d[PFT_FORMULA_MAX]; } mine;
+	char * all;
 	pft_ic_prog pr[PFT_FORMULA_MAX];
 	pft_grid g;
-	pft_comm * c = comm();
-	const int nprocs = pft_comm_size(c);
-	int rc = 0, r, f, off = 0, entries = 0, bad = 0, first_bad = 0;
-	size_t at, used;
+	const int nprocs = pft_comm_size(comm());
+	int rc, crc, r, f, off = 0, entries = 0;
+	size_t used;
 	if(!global) return -2;
-	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
-	if(R.in_callback && nprocs > 1) return -2;
+	if((rc = resident_state(1))) return rc;
 	if(nprocs > PFT_DIAG_MAX_RANKS) return -2;
 	if(nprog < 1 || nprog > PFT_FORMULA_MAX || !lens || !ops || !args || pft_model_get_grid(&g)) rc = -2;
 	for(f = 0; f < nprog && !rc; f++) {
@@ -844,15 +846,9 @@ int pft_solver_formulas(int nprog, const int * lens, const int * ops, const doub
 		rc = pft_formula_compile(&g, lens[f], ops + off, args + off, &pr[f]);
 		off += lens[f];
 	}
-	if(nprocs > 1) {
-		long long v = rc == -1 ? 3 : (rc == -2 ? 2 : (rc == 1 ? 1 : (rc ? 3 : 0)));
-		int crc = pft_comm_allreduce_max_i64(c, &v);
-		if(crc) {
-			for(f = 0; f < PFT_FORMULA_MAX; f++) pft_ic_prog_free(&pr[f]);
-			R.last_status = crc;
-			return PFT_SOLVE_DEVICE_ERROR;
-		}
-		rc = v == 3 ? -1 : (v == 2 ? -2 : (v == 1 ? 1 : 0));
+	if((crc = compile_agree(&rc))) {
+		R.last_status = crc;
+		rc = PFT_SOLVE_DEVICE_ERROR;
 	}
 	if(rc) {
 		for(f = 0; f < PFT_FORMULA_MAX; f++) pft_ic_prog_free(&pr[f]);
@@ -861,45 +857,15 @@ int pft_solver_formulas(int nprog, const int * lens, const int * ops, const doub
 	memset(&mine, 0, sizeof mine);
 	rc = pft_slab_formulas(R.slab, PFT_BUF_X, nprog, pr, mine.d, per_plane);
 	for(f = 0; f < PFT_FORMULA_MAX; f++) pft_ic_prog_free(&pr[f]);
-	mine.status = rc;
-	if(nprocs == 1) {
-		if(rc) { R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
-		for(f = 0; f < nprog; f++) {
-			global[f] = mine.d[f];
-			if(local) local[f] = mine.d[f];
-		}
-		return 0;
-	}
 	used = offsetof(struct formula_msg, d) + (size_t)nprog * sizeof(pft_fdiag);
-	/* (a failed allocation is this rank's failure, met after the rounds like any other) */
-	all = (struct formula_msg *)malloc((size_t)nprocs * sizeof *all);
-	if(!all && !mine.status) mine.status = -1;
-	for(at = 0; at < used; at += ROUND) {
-		const int bytes = (int)(used - at < ROUND ? used - at : ROUND);
-		if((rc = pft_comm_allgather(c, (const char *)&mine + at, bytes, piece))) {
-			free(all);
-			R.last_status = rc;
-			return PFT_SOLVE_DEVICE_ERROR;
-		}
-		if(at == 0)
-			for(r = 0; r < nprocs; r++) {
-				long long st;
-				memcpy(&st, piece + (size_t)r*bytes, sizeof st);
-				if(st) { bad = 1; if(!first_bad) first_bad = (int)st; }
-			}
-		for(r = 0; r < nprocs && all; r++) memcpy((char *)&all[r] + at, piece + (size_t)r*bytes, bytes);
-	}
-	if(bad) {
-		free(all);
-		R.last_status = mine.status ? (int)mine.status : first_bad;
-		return PFT_SOLVE_DEVICE_ERROR;
-	}
+	if((rc = gather_records(rc, &mine, used, &all))) return rc;
 	for(f = 0; f < nprog; f++) {
-		global[f] = all[0].d[f];
-		for(r = 1; r < nprocs; r++) pft_fdiag_combine(&global[f], &all[r].d[f]);
+		global[f] = ((const struct formula_msg *)all)->d[f];
+		for(r = 1; r < nprocs; r++)
+			pft_fdiag_combine(&global[f], &((const struct formula_msg *)(all + (size_t)r*used))->d[f]);
 		if(local) local[f] = mine.d[f];
 	}
-	free(all);
+	drop_records(all, &mine);
 	return 0;
 }
 
@@ -918,29 +884,25 @@ int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, cons
                     long long * plane_counts)
 {
 	/* f13: the histogram of the device-resident x, under pft_solver_diag's rules.  Every rank checks
-	   the edges and compiles both programs first; the outcome (1 not device-exact, -2 a bad program
-	   or bad edges, the same on every rank; -1 out of memory, local: -1 over -2 over 1) and a 64-bit
-	   hash of nbins, the edges and both programs travel in the first allgather round, so that ranks
-	   that were given different histograms all answer -2 before any device work.  Then each rank
-	   counts its slab and the record travels with its status in rounds of at most 256 bytes, as
-	   pft_solver_formulas' do; the records are merged in rank order */
-	enum { ROUND = 256 };
+	   the edges and compiles both programs first; the outcome (compile_rank; bad edges are -2 as a
+	   bad program is) and a 64-bit hash of nbins, the edges and both programs travel in one
+	   allgather, so that ranks that were given different histograms all answer -2 before any device
+	   work.  Then each rank counts its slab and the used part of its message travels
+	   (gather_records); the records are merged in rank order */
 	struct hist_first { long long code; unsigned long long hash; };
-	struct hist_msg { long long status; pft_hist_head h; long long counts[PFT_HIST_MAX_BINS]; };
-	struct hist_msg * all, * mine;   /* (loopback ranks are threads of one process: nothing static) */
-	char piece[PFT_DIAG_MAX_RANKS * ROUND];
+	struct hist_msg { long long status; pft_hist_head h; long long counts[PFT_HIST_MAX_BINS]; } mine;
+	const struct hist_msg * m;
+	char * all;
 	struct hist_first first, firsts[PFT_DIAG_MAX_RANKS];
 	pft_ic_prog pv, pm;
 	pft_grid g;
 	pft_comm * c = comm();
 	const int nprocs = pft_comm_size(c);
 	const int masked = mops || margs || nm;
-	int rc = 0, r, bad = 0, first_bad = 0;
-	long long my_status = 0;
-	size_t at, used;
+	int rc, r;
+	size_t used;
 	if(!global || !global_counts) return -2;
-	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
-	if(R.in_callback && nprocs > 1) return -2;
+	if((rc = resident_state(1))) return rc;
 	if(nprocs > PFT_DIAG_MAX_RANKS) return -2;
 	memset(&pv, 0, sizeof pv);
 	memset(&pm, 0, sizeof pm);
@@ -964,7 +926,7 @@ int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, cons
 	if(nprocs > 1) {
 		int crc;
 		long long v = 0;
-		first.code = rc == -1 ? 3 : (rc == -2 ? 2 : (rc == 1 ? 1 : (rc ? 3 : 0)));
+		first.code = compile_rank(rc);
 		crc = pft_comm_allgather(c, &first, (int)sizeof first, firsts);
 		if(crc) {
 			pft_ic_prog_free(&pv);
@@ -975,67 +937,30 @@ int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, cons
 		for(r = 0; r < nprocs; r++) if(firsts[r].code > v) v = firsts[r].code;
 		/* (ranks that all compiled: the same histogram on every one of them, or -2) */
 		for(r = 1; r < nprocs && !v; r++) if(firsts[r].hash != firsts[0].hash) v = 2;
-		rc = v == 3 ? -1 : (v == 2 ? -2 : (v == 1 ? 1 : 0));
+		rc = compile_code(v);
 	}
 	if(rc) {
 		pft_ic_prog_free(&pv);
 		pft_ic_prog_free(&pm);
 		return rc;
 	}
-	mine = (struct hist_msg *)calloc(1, sizeof *mine);
-	if(mine) rc = pft_slab_hist(R.slab, PFT_BUF_X, &pv, masked ? &pm : NULL, nbins, edges, &mine->h, mine->counts,
-	                            plane_heads, plane_counts);
+	memset(&mine, 0, sizeof mine);
+	rc = pft_slab_hist(R.slab, PFT_BUF_X, &pv, masked ? &pm : NULL, nbins, edges, &mine.h, mine.counts, plane_heads,
+	                   plane_counts);
 	pft_ic_prog_free(&pv);
 	pft_ic_prog_free(&pm);
-	if(nprocs == 1) {
-		if(!mine) return -1;
-		if(rc) { free(mine); R.last_status = rc; return PFT_SOLVE_DEVICE_ERROR; }
-		*global = mine->h;
-		memcpy(global_counts, mine->counts, sizeof(long long) * (size_t)nbins);
-		if(local) *local = mine->h;
-		if(local_counts) memcpy(local_counts, mine->counts, sizeof(long long) * (size_t)nbins);
-		free(mine);
-		return 0;
-	}
 	used = offsetof(struct hist_msg, counts) + (size_t)nbins * sizeof(long long);
-	/* (a failed allocation is this rank's failure, met after the rounds like any other) */
-	all = (struct hist_msg *)malloc((size_t)nprocs * sizeof *all);
-	for(at = 0; at < used; at += ROUND) {
-		const int bytes = (int)(used - at < ROUND ? used - at : ROUND);
-		char out[ROUND];
-		memset(out, 0, sizeof out);
-		if(mine) memcpy(out, (const char *)mine + at, bytes);
-		if(at == 0) {
-			my_status = !mine || !all ? (rc ? rc : -1) : rc;
-			memcpy(out, &my_status, sizeof my_status);
-		}
-		if((rc = pft_comm_allgather(c, out, bytes, piece))) {
-			free(all);
-			free(mine);
-			R.last_status = rc;
-			return PFT_SOLVE_DEVICE_ERROR;
-		}
-		if(at == 0)
-			for(r = 0; r < nprocs; r++) {
-				long long st;
-				memcpy(&st, piece + (size_t)r*bytes, sizeof st);
-				if(st) { bad = 1; if(!first_bad) first_bad = (int)st; }
-			}
-		for(r = 0; r < nprocs && all; r++) memcpy((char *)&all[r] + at, piece + (size_t)r*bytes, bytes);
+	if((rc = gather_records(rc, &mine, used, &all))) return rc;
+	m = (const struct hist_msg *)all;
+	*global = m->h;
+	memcpy(global_counts, m->counts, sizeof(long long) * (size_t)nbins);
+	for(r = 1; r < nprocs; r++) {
+		m = (const struct hist_msg *)(all + (size_t)r*used);
+		pft_hist_combine(nbins, global, global_counts, &m->h, m->counts);
 	}
-	if(bad) {
-		free(all);
-		free(mine);
-		R.last_status = my_status ? (int)my_status : first_bad;
-		return PFT_SOLVE_DEVICE_ERROR;
-	}
-	*global = all[0].h;
-	memcpy(global_counts, all[0].counts, sizeof(long long) * (size_t)nbins);
-	for(r = 1; r < nprocs; r++) pft_hist_combine(nbins, global, global_counts, &all[r].h, all[r].counts);
-	if(local) *local = mine->h;
-	if(local_counts) memcpy(local_counts, mine->counts, sizeof(long long) * (size_t)nbins);
-	free(all);
-	free(mine);
+	if(local) *local = mine.h;
+	if(local_counts) memcpy(local_counts, mine.counts, sizeof(long long) * (size_t)nbins);
+	drop_records(all, &mine);
 	return 0;
 }
 
@@ -1093,7 +1018,7 @@ int pft_solver_ic_formulas_device(int nprog, const int * qs, const int * lens, c
 	pft_ic_tables tb;
 	pft_ic_prog * pr;
 	double * store = NULL;
-	int * istore = NULL, unclean = 0, rc = 0, ret = 0, p, off = 0, ok = 1;
+	int * istore = NULL, unclean = 0, rc = 0, crc, ret = 0, p, off = 0, ok = 1;
 	if(R.max_n == 0) return -3;
 	if(nprog < 1 || !qs || !lens || !ops || !args || pft_model_get_grid(&g)) return -2;
 	pr = (pft_ic_prog*)calloc(nprog, sizeof(pft_ic_prog));
@@ -1110,18 +1035,11 @@ int pft_solver_ic_formulas_device(int nprog, const int * qs, const int * lens, c
 		off += lens[p];
 		if(rc) ok = 0;
 	}
-	if(pft_comm_size(comm()) > 1) {
-		long long v = rc == -1 ? 3 : (rc == -2 ? 2 : (rc == 1 ? 1 : (rc ? 3 : 0)));
-		int crc = pft_comm_allreduce_max_i64(comm(), &v);
-		if(crc) {
-			for(p = 0; p < nprog; p++) pft_ic_prog_free(&pr[p]);
-			free(pr);
-			R.last_status = crc;
-			return PFT_SOLVE_DEVICE_ERROR;
-		}
-		rc = v == 3 ? -1 : (v == 2 ? -2 : (v == 1 ? 1 : 0));
-		ok = rc == 0;
+	if((crc = compile_agree(&rc))) {
+		R.last_status = crc;
+		rc = PFT_SOLVE_DEVICE_ERROR;
 	}
+	ok = rc == 0;
 	if(!ok) {
 		for(p = 0; p < nprog; p++) pft_ic_prog_free(&pr[p]);
 		free(pr);
@@ -1183,15 +1101,13 @@ static int snap_agree(int rc)
 
 int pft_solver_snapshot_write(const char * path, const double * param, const pft_snapshot_info * info, int flags)
 {
-	pft_comm * c = comm();
-	const int nprocs = pft_comm_size(c), version = (flags >> 8) & 3;
+	const int version = (flags >> 8) & 3;
 	pft_snapshot_ranges r;
 	void * image = NULL;
 	int rc = 0;
 	if(!path || !param || !info || version > 2) return -2;
 	/* the validity rules of pft_solver_diag: never a stale file */
-	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
-	if(R.in_callback && nprocs > 1) return -2;
+	if((rc = resident_state(1))) return rc;
 	/* rank 0 writes the header; the agreed status is also the barrier before the other ranks open
 	   the file */
 	if(R.slab_grid.rank == 0) rc = pft_snapshot_create(path, &R.slab_grid, param, info, version);
@@ -1221,15 +1137,13 @@ static int region_of_slab(const pft_region * region, pft_region * loc, int * kfi
 int pft_solver_snapshot_region_write(const char * path, const double * param, const pft_snapshot_info * info,
                                      const pft_region * region, int flags)
 {
-	pft_comm * c = comm();
-	const int nprocs = pft_comm_size(c), version = (flags >> 8) & 3;
+	const int version = (flags >> 8) & 3;
 	pft_snapshot_ranges r;
 	pft_region loc;
 	void * image = NULL;
 	int rc = 0, kfirst;
 	if(!path || !param || !info || !region || version > 2) return -2;
-	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
-	if(R.in_callback && nprocs > 1) return -2;
+	if((rc = resident_state(1))) return rc;
 	/* the region is judged against the whole grid, which every rank holds: the same answer everywhere */
 	if(pft_region_check(&R.slab_grid, region)) return -2;
 	if(R.slab_grid.rank == 0) rc = pft_snapshot_create_region(path, &R.slab_grid, region, param, info, version);
@@ -1254,7 +1168,7 @@ int pft_solver_region(const pft_region * region, double * out_native)
 	int rc, kfirst;
 	size_t n, w;
 	if(!region) return -2;
-	if(R.max_n == 0 || !R.slab || !(R.device_valid || R.in_callback)) return -3;
+	if((rc = resident_state(0))) return rc;
 	if((rc = region_of_slab(region, &loc, &kfirst))) return rc;
 	n = 3 * (size_t)loc.count[0] * (size_t)loc.count[1] * (size_t)loc.count[2];
 	if(n == 0) return 0;
