@@ -1332,10 +1332,23 @@ struct PairLds {
 // neighbours from the LDS field planes L[q] around slot p (even / odd halves, row pitch LWP); the
 // x-face between the pair's cells is evaluated once and the z-face below is carried in fz
 // (rhs_cell_f, bit-exact), as in merson_fused
-template <int MODE, int LWP>
+// (HN: field 2's x/y neighbours come from hn, read by pair_nbr2 ahead of the call, and L2 is not
+// touched: the staggered stage B, whose gl plane in lA is being overwritten while it runs)
+struct PairNbr {
+  dbl2 ym, yp;      // the pairs one row below / above
+  double xm, xp;    // the cells left of the even / right of the odd cell
+};
+template <int LWP>
+__device__ __forceinline__ PairNbr pair_nbr2(const double* L2, int p, int xmc, int xpc)
+{
+  using LD = PairLds;
+  return PairNbr{LD::ld(L2, p - LWP), LD::ld(L2, p + LWP), LD::cell(L2, p - 1, xmc), LD::cell(L2, p + 1, xpc)};
+}
+template <int MODE, int LWP, bool HN = false>
 __device__ __forceinline__ void pair_rhs(const pft_consts& c, const double* L0, const double* L1, const double* L2,
                                          int p, int xmc, int xpc, const dbl2* zm, const dbl2* zc, const dbl2* zp,
-                                         const double* nz, FaceT* fz, double* du, double* dp)
+                                         const double* nz, FaceT* fz, double* du, double* dp,
+                                         const PairNbr* hn = nullptr)
 {
   constexpr bool FLUX = MODE != 10 && MODE != 11;
   using LD = PairLds;
@@ -1345,6 +1358,11 @@ __device__ __forceinline__ void pair_rhs(const pft_consts& c, const double* L0, 
   dbl2 ym2[3], yp2[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
+    if (HN && q == 2) {
+      ym2[q] = hn->ym;
+      yp2[q] = hn->yp;
+      continue;
+    }
     ym2[q] = LD::ld(L[q], p - LWP);
     yp2[q] = LD::ld(L[q], p + LWP);
   }
@@ -1358,8 +1376,13 @@ __device__ __forceinline__ void pair_rhs(const pft_consts& c, const double* L0, 
       col[q].c = cen;
       // the cell of the pair to the left / right next to this pair: its odd / even cell, or the
       // other one where that slot holds a mirrored position in natural order (xmc / xpc)
-      col[q].xm = s == 0 ? LD::cell(L[q], p - 1, xmc) : zc[q][0];
-      col[q].xp = s == 0 ? zc[q][1] : LD::cell(L[q], p + 1, xpc);
+      if (HN && q == 2) {
+        col[q].xm = s == 0 ? hn->xm : zc[q][0];
+        col[q].xp = s == 0 ? zc[q][1] : hn->xp;
+      } else {
+        col[q].xm = s == 0 ? LD::cell(L[q], p - 1, xmc) : zc[q][0];
+        col[q].xp = s == 0 ? zc[q][1] : LD::cell(L[q], p + 1, xpc);
+      }
       col[q].ym = ym2[q][s];
       col[q].yp = yp2[q][s];
       col[q].zm = zm[q][s];
@@ -1408,6 +1431,37 @@ __device__ __forceinline__ void pair_pos(int v, int bw, int ty, int& px, int& py
 
 template <int N>
 using pft_ic = std::integral_constant<int, N>;
+
+// The stagger of the pair kernels' wave halves.  The two waves of a
+// SIMD, w and w + 4, run the same plane step between the same two barriers; with the stagger the
+// late half (waves 4-7) passes a step's barrier between stage A and stage B instead of at the
+// step's end, so its stage B runs in the next barrier interval, beside the early half's top and
+// stage A.  Every wave still passes one barrier per step and runs the same text in the same order.
+// Which instances keep it (measured, 400^3 and 200^3, profiles/f14_stagger_ab.txt): pair 2+3 on
+// the 22-pair pitch in calc_modes 0 and 1, +1.0% and +1.4% on the step.  Pair 4+5 lost 1.4% with
+// it (tied at best, with a static priority), calc_mode 2 lost 3.6% and the 12-pair pitch 3% at
+// 200^3: they keep the barrier at the step's end, and so do modes 10 and 11, which no benchmark
+// measures.
+// -DPFT_PAIR_STAGGER=0: every wave at the step's end, as before (A/B); a bit mask otherwise
+// (1: pair 2+3, 2: pair 4+5, 4: the 12-pair pitch too, 8: every calc_mode).  -DPFT_PAIR_STAGGER_ODD=1: the odd waves
+// as the late half (the control: partners are w / w + 4, and it lost).
+// -DPFT_PAIR_PRIO: the s_setprio scheme of staggered kernels, 0: the per-phase flips (kept),
+// 1: none, 2: one static s_setprio 1 for the late half.
+#ifndef PFT_PAIR_STAGGER
+#define PFT_PAIR_STAGGER 1
+#endif
+#ifndef PFT_PAIR_STAGGER_ODD
+#define PFT_PAIR_STAGGER_ODD 0
+#endif
+#ifndef PFT_PAIR_PRIO
+#define PFT_PAIR_PRIO 0
+#endif
+constexpr bool pair_stagger(int SA, int MODE, bool GLX, int LWP)
+{
+  (void)GLX;
+  return (PFT_PAIR_STAGGER & (SA == 2 ? 1 : 2)) && (LWP == 22 || (PFT_PAIR_STAGGER & 4)) &&
+         (MODE == 0 || MODE == 1 || (PFT_PAIR_STAGGER & 8));
+}
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Warray-bounds"
@@ -1550,6 +1604,11 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
   dbl2 IA[3][3];
   dbl2 glm = zero2;     // GLB: gl's input at this position, plane mm - 2 (stage B's z neighbour below)
   FaceT fzA[2], fzB[2];
+  // the stagger (pair_stagger above): waves 4-7, the SIMDs' second waves, are the late half
+  constexpr bool STG = pair_stagger(SA, MODE, GLX, LWP);
+  const bool late = STG && (PFT_PAIR_STAGGER_ODD ? (wid & 1) != 0 : wid >= PFT_PBLOCK / 128);
+  constexpr bool PRIOF = !STG || PFT_PAIR_PRIO == 0;   // the per-phase s_setprio flips
+  if (STG && PFT_PAIR_PRIO == 2 && late) __builtin_amdgcn_s_setprio(1);
 
   // prologue: stage A's input of planes mA0 - 1 (if any) and mA0 into the ring (slots 2 and 0);
   // operands of mA0 kept, of mA0 + 1 in flight.  (kb >= ke: an empty chunk, which still takes
@@ -1665,15 +1724,21 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       if (SDY || mm + 2 <= mlast) pair_load<SA>(A0, pbo(mm + 2), rnn);   // look-ahead
     }
     const int kB = mm - 1;                                   // stage B's plane
+    constexpr int sB = (PH + 2) % 3, sBm = (PH + 1) % 3, sBp = PH;   // slots of planes kB, kB-1, kB+1
+    // (GLB: gl's plane from lA, whose rows start one row earlier: slot posB + LWP there)
+    const double* lBgl = GLB ? &lA[sB][2][2 * LWP] : &lB[sB][NBQ - 1][0];
     PairRaw ro;
+    PairNbr hn;
     {
       PFT_PAIR_BIND(A1, C1);
       // The two waves of a SIMD (w and w + 4) run the same phase between two barriers, so their
       // stalls coincide.  Waves 0-3 get issue precedence in stage A (pair 2+3: waves 4-7 in stage
       // B, pair 4+5: nobody), so the two drift apart and fill each other's stalls.  Measured (A/B,
       // one box): pair 4+5 0.496 -> 0.480 ms; pair 2+3 0.425 -> 0.403 ms.
-      if ((threadIdx.x >> 8) == 0) __builtin_amdgcn_s_setprio(2);
-      else __builtin_amdgcn_s_setprio(0);
+      if (PRIOF) {
+        if ((threadIdx.x >> 8) == 0) __builtin_amdgcn_s_setprio(2);
+        else __builtin_amdgcn_s_setprio(0);
+      }
       dbl2 (&ka)[2] = KA[PH];
       ka[0] = ka[1] = zero2;
       if ((SDY || mm <= mA1) && isA) {
@@ -1710,11 +1775,23 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         }
       }
     }
+    if constexpr (STG) {
+      // The stagger: the late half passes this step's barrier here, between stage A and stage B
+      // (the early half at the step's end), so its stage B runs beside the early half's top and
+      // stage A of the next step.  The top of that step overwrites lA's slot sB, whose field 2
+      // stage B reads at its x/y neighbours (GLB): both halves read those six doubles here, where
+      // the slot is intact, and the barrier's lgkmcnt(0) completes them.  The chunk's last step
+      // has no barrier in either half.  (The hazard table is beside the z-loop.)
+      if (GLB && (SDY || kB >= kb) && isB) hn = pair_nbr2<LWP>(lBgl, posB, xmcB, xpcB);
+      if (late && (SDY || mm != ke)) __syncthreads();
+    }
     {
       PFT_PAIR_BIND(A2, C2);
-      if (SA == 4) __builtin_amdgcn_s_setprio(0);
-      else if ((threadIdx.x >> 8) == 0) __builtin_amdgcn_s_setprio(0);
-      else __builtin_amdgcn_s_setprio(2);
+      if (PRIOF) {
+        if (SA == 4) __builtin_amdgcn_s_setprio(0);
+        else if ((threadIdx.x >> 8) == 0) __builtin_amdgcn_s_setprio(0);
+        else __builtin_amdgcn_s_setprio(2);
+      }
       // operands of plane kB for stage B's outputs (4+5).  OPL: from lO.  Otherwise loaded a
       // second time, after stage A (in registers they would need ~60 VGPRs more than the 255 in
       // use), and NOT an L2 hit: their first load was the look-ahead three planes earlier, and
@@ -1746,7 +1823,6 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         pair_load<SA, !GLX>(A2, pbo(kB), ro);
       }
       if ((SDY || kB >= kb) && isB) {
-        constexpr int sB = (PH + 2) % 3, sBm = (PH + 1) % 3, sBp = PH;   // slots of planes kB, kB-1, kB+1
         const int lo = posB;
         if (!SDY && kB == n3 - 1 && whi) {
           // top wall: the ghost values of plane n3 at this position (as in stage A above)
@@ -1776,9 +1852,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         double du[2], dp[2];
         const unsigned e0 = pbo(kB);
         const double* nz = SDY ? nullptr : A2.noise ? A2.noise + (long)kB * A2.plane + (long)apo : nullptr;
-        // (GLB: gl's plane from lA, whose rows start one row earlier: slot lo + LWP there)
-        const double* lBgl = GLB ? &lA[sB][2][2 * LWP] : &lB[sB][NBQ - 1][0];
-        pair_rhs<MODE, LWP>(C2, lB[sB][0], lB[sB][1], lBgl, lo, xmcB, xpcB, zm, zc, zp, nz, fzB, du, dp);
+        pair_rhs<MODE, LWP, STG && GLB>(C2, lB[sB][0], lB[sB][1], lBgl, lo, xmcB, xpcB, zm, zc, zp, nz, fzB, du, dp, &hn);
         if (SA == 2) {
           stb(A2.out, e0, dbl2{du[0], du[1]});                   // K3 (hybrid2.c:412-429)
           stb(A2.out + A2.fs, e0, dbl2{dp[0], dp[1]});
@@ -1805,10 +1879,42 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       }
     }
     if (!SDY && mm == ke) return false;
-    __syncthreads();
+    if (!STG || !late) __syncthreads();
     return true;
   };
 
+  // The staggered schedule and its LDS accesses (STG; tests/test_pair_stagger_model.py restates
+  // this table and checks it).  Step j runs T_j (the top), A_j (stage A, plane j), B_j (stage B,
+  // plane j - 1); bar_j is its barrier and interval I_j lies between bar_{j-1} and bar_j.  The
+  // early half runs T_j A_j B_j bar_j, the late half T_j A_j bar_j B_j: the early half's I_j holds
+  // T_j A_j B_j, the late half's B_{j-1} T_j A_j.  Both skip bar_j on the chunk's last step, so
+  // every wave passes the prologue's barrier, one per step but the last, and the epilogue's: the
+  // same count on every path (an empty chunk: none but the epilogue's).  slot(p) = (p - mA0) mod 3.
+  //
+  //   access                      ring slot, fields     position    interval: early / late
+  //   T_j   glm read (4+5, GLB)   lA slot(j+1), 2       own         I_j / I_j
+  //   T_j   plane j+1 in          lA slot(j+1), 0-2     own, extras I_j / I_j
+  //   A_j   top wall ghost        lA slot(j+1), 0-2     own         I_j / I_j   (T_j stores nothing there)
+  //   A_j   x/y neighbours        lA slot(j), 0-2       neighbours  I_j / I_j   (actA's: the same reads)
+  //   A_j   z column (4+5)        lA slot(j-1 .. j+1)   own         I_j / I_j
+  //   A_j   stage B's input out   lB slot(j), 0-NBQ     own         I_j / I_j   (bottom wall: slot(j-1) too)
+  //   hoist gl x/y neighbours     lA slot(j-1), 2       neighbours  I_j / I_j   (GLB; ahead of bar_j)
+  //   B_j   top wall ghost        lB slot(j), 0-NBQ     own         I_j / I_j+1 (last step only: no I_j+1)
+  //   B_j   x/y neighbours        lB slot(j-1), 0-NBQ   neighbours  I_j / I_j+1
+  //   B_j   z column              lB slot(j-2 .. j)     own         I_j / I_j+1
+  //   B_j   gl centre, above      lA slot(j-1), slot(j), 2  own     I_j / I_j+1 (GLB, 4+5; registers in 2+3)
+  //   B_j   operands              lO                    own         I_j / I_j+1
+  //
+  // A neighbour read is safe when its slot and field are written in an earlier interval and not in
+  // its own.  lA slot(j) is written in I_{j-1} (T_{j-1}) and again in I_{j+2}: A_j's reads in I_j
+  // are safe in both halves.  lB slot(j-1) is written in I_{j-1} (A_{j-1}) and again in I_{j+2}
+  // (A_{j+2}): B_j's reads in I_j or I_{j+1} are safe.  The early half's A_{j+1} writes lB
+  // slot(j+1) = slot(j-2) while the late half's B_j reads that slot, but each at its own position.
+  // The hazard is B_j's gl neighbours under GLB: lA slot(j-1) is overwritten by T_{j+1} in I_{j+1},
+  // where the late half's B_j runs -- hence the hoist into I_j, where the writes go to slot(j+1)
+  // (T_j and stage A's top wall).  Own-position accesses stay in program order, which is the same
+  // in both halves.  (Threads beyond the positions shadow the last one: the same values into the
+  // same slot in the same interval as its owner, T_j's row of the table.)
   if (kb < ke) {
     // The steady range.  A step at plane mm has every chunk-position test of step() decided when
     //   mm + 2 <= mlast   the look-ahead, the next plane's stage-A input and the extras' pair of
@@ -1829,7 +1935,9 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
     // whose gl holds a -0.0 or a NaN), the one kernel that kept a spilled VGPR with the steady
     // loop: it stays the single z-loop it was.  The 12-pair pitch keeps the single loop too:
     // 200^3 (100 x 100 planes) ran 1.6% slower with the steady loop, outside the run-to-run range
-    // (profiles/f9_bench_ab.txt).
+    // (profiles/f9_bench_ab.txt).  The stagger (STG) is decided per instance as well, by
+    // pair_stagger above the kernel: pair 2+3 on the 22-pair pitch in calc_modes 0 and 1 has it, general and
+    // steady steps alike; pair 4+5 and the 12-pair pitch keep every wave's barrier at the step's end.
     constexpr bool STEADY = LWP == 22 && !(SA == 4 && MODE == 0 && !GLX);
     const int msteady = a.noise ? -(1 << 30) : mlast - 4;        // last first plane of a steady triple
     for (int mm = mA0;; mm += 3) {
