@@ -233,18 +233,22 @@ int pft_slab_region_export(pft_slab * s, int buf, const pft_region * r_local, in
    range (for boundary-first splitting), -1/-1 = all planes. */
 int pft_slab_stage(pft_slab * s, int stage, double t_stage, double coef, double h,
                    int k_begin, int k_end);
-/* k_begin value selecting the slab's two boundary planes (0 and n3-1) in one launch */
+/* k_begin codes of pft_slab_stage, pft_slab_stage_spec and pft_slab_pair_range (k_end is ignored);
+   csrc/pft_zplan.h turns each into the launch's z-chunks.
+   The slab's two boundary planes (0 and n3-1) in one launch (stage launches only) */
 #define PFT_K_BOUNDARY (-2)
-/* k_begin value selecting planes 0, 1 and n3-2, n3-1 in one launch (what the z-neighbours' pair
-   kernels read: the two-plane halo) */
+/* planes 0, 1 and n3-2, n3-1 in one launch (what the z-neighbours' pair kernels read: the two-plane
+   halo) */
 #define PFT_K_BOUNDARY2 (-3)
-/* pair kernels only: the PFT_K_BOUNDARY2 chunks lead the grid of the interior launch [2, n3-2), one
-   launch; the copy-engine exchange that follows starts when those workgroups are done
-   (pft_slab_boundary_inline) */
+/* the PFT_K_BOUNDARY2 chunks lead the grid of the interior launch [2, n3-2), one launch; the
+   copy-engine exchange that follows starts when those workgroups are done
+   (pft_slab_boundary_inline).  Pair kernels and merson_fused stage launches (not gated, not the cache
+   kernel), n3 >= 5; -2 where the launcher cannot serve it */
 #define PFT_K_INLINE (-4)
-/* pair kernels only: the whole slab in one launch whose first workgroups are the first and the last
-   z-chunk of every tile column (at least three chunks); the copy-engine exchange that follows starts
-   when those are done */
+/* the whole slab in one launch whose first workgroups are the first and the last z-chunk of every
+   tile column (at least three chunks, the end chunks of two planes or more; where the slab cannot be
+   cut so, PFT_K_INLINE instead); the copy-engine exchange that follows starts when those are done.
+   The same launchers as PFT_K_INLINE */
 #define PFT_K_ENDS_FIRST (-5)
 
 /* K = f(input) only (RK_RightHandSide semantics), input/output buffer indices */

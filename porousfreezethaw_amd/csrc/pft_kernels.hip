@@ -22,6 +22,9 @@
 // The reductions (pft_reduce.hip) and the snapshots (pft_snap.hip) are translation units of their
 // own over pft_slab.h, which holds the slab object and what the files share.
 #include "pft_slab.h"
+#include "pft_zplan.h"
+static_assert(PFT_K_BOUNDARY == PFT_ZP_BOUNDARY && PFT_K_BOUNDARY2 == PFT_ZP_BOUNDARY2 && PFT_K_INLINE == PFT_ZP_INLINE &&
+              PFT_K_ENDS_FIRST == PFT_ZP_ENDS_FIRST, "pft_zplan.h restates the range codes of pft_hip.h");
 
 #include "pft_cosh.h"
 #include "pft_ic_ops.h"
@@ -277,9 +280,8 @@ struct StageArgs {
   int has_below, has_above;
   int k_begin, k_end, kz, ntile, nchunk;
   int kspan;           // planes a chunk processes from its start (kz, or 1 for the boundary planes)
-  // inline boundary (merson_fused; as PairArgs): the first nbw workgroups produce the planes the
-  // exchange sends and count themselves in *bdone; bends 1: the first and last chunk of every tile
-  // column, 0: two-plane chunks at each end; the other nint workgroups run chunks c0 ..
+  // inline boundary (merson_fused; pft_zplan.h): the first nbw workgroups produce the planes the
+  // exchange sends and count themselves in *bdone
   int nbw, bends, c0, nint;
   unsigned long long* bdone;
   double T_top;        // Dirichlet value T_top(t_stage), equation.c:110
@@ -541,13 +543,6 @@ __global__ __launch_bounds__(256) void eps_reduce_kernel(const unsigned long lon
 }
 
 
-__host__ __device__ __forceinline__ int xcd_remap(int b, int n)
-{
-  // bijective: the blocks the dispatcher deals to one XCD (b % 8 equal) get consecutive ids
-  const int q = n >> 3, r = n & 7, x = b & 7, l = b >> 3;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + l;
-}
-
 template <int STAGE, bool GLS>
 __device__ __forceinline__ double combine(const StageArgs& a, int q, long o, double K, double* m, bool& nf)
 {
@@ -581,14 +576,13 @@ __device__ __forceinline__ double combine(const StageArgs& a, int q, long o, dou
 template <int STAGE, int MODE, bool GLS>
 __global__ __launch_bounds__(PFT_BLOCK) void merson_stage(StageArgs a, pft_consts c)
 {
-  const int lin = xcd_remap(blockIdx.x, a.ntile * a.nchunk);
-  const int tile = lin % a.ntile, chunk = lin / a.ntile;
+  int tile, chunk, kb, ke;
+  pft_zplan_chunk_flat((int)blockIdx.x, a.ntile, a.nchunk, &tile, &chunk);
   const int cell = tile * PFT_BLOCK + threadIdx.x;
   const bool active = cell < a.plane;
   const int cc = active ? cell : a.plane - 1;
   const int j = cc / a.n1, i = cc - j * a.n1;
-  const int kb = a.k_begin + chunk * a.kz;
-  const int ke = min(kb + a.kspan, a.k_end);
+  pft_zplan_planes(chunk, false, a.n3, a.k_begin, a.k_end, a.kz, a.kspan, &kb, &ke);
 
   // neighbour offsets within a plane, mirrored at the x/y walls (equation.c:137-161)
   const int oxm = i > 0 ? -1 : 0, oxp = i < a.n1 - 1 ? 1 : 0;
@@ -840,12 +834,9 @@ __global__ __launch_bounds__(PFT_FBLOCK) __attribute__((amdgpu_waves_per_eu(STAG
     return;
   }
   const int ntx = (a.n1 + TX - 1) / TX;
-  // inline boundary: the leading workgroups (dispatched first) produce the planes the exchange sends
-  const bool bw = (int)blockIdx.x < a.nbw;
-  const int lin = bw ? xcd_remap(blockIdx.x, a.nbw) : xcd_remap(blockIdx.x - a.nbw, a.nint);
-  const int tile = lin % a.ntile, cq = lin / a.ntile;
-  const int chunk = bw ? (a.bends ? (cq ? a.nchunk - 1 : 0) : cq) : a.c0 + cq;
-  const bool bshort = bw && !a.bends;
+  int tile, chunk, kb, ke;
+  bool bw, bshort;
+  pft_zplan_chunk((int)blockIdx.x, a.ntile, a.nchunk, a.nbw, a.bends, a.c0, a.nint, &tile, &chunk, &bw, &bshort);
   const int x0 = (tile % ntx) * TX, y0 = (tile / ntx) * TY;
   // threads beyond the WX x TY tile (256 > WX * TY) shadow the tile's last thread: the same loads
   // and LDS writes (same values to the same slots), no global stores
@@ -854,8 +845,7 @@ __global__ __launch_bounds__(PFT_FBLOCK) __attribute__((amdgpu_waves_per_eu(STAG
   const int i0 = x0 + 2 * tx, j = y0 + ty;
   const bool active = (i0 < a.n1) && (j < a.n2) && (int)threadIdx.x < WX * TY;
   const long po = (long)(j < a.n2 ? j : a.n2 - 1) * a.n1 + (i0 < a.n1 ? i0 : a.n1 - 2);
-  const int kb = bshort ? chunk * (a.n3 - 2) : a.k_begin + chunk * a.kz;
-  const int ke = bshort ? kb + 2 : min(kb + a.kspan, a.k_end);
+  pft_zplan_planes(chunk, bshort, a.n3, a.k_begin, a.k_end, a.kz, a.kspan, &kb, &ke);
   const int lo = (ty + 1) * LW + 2 + 2 * tx;
 
   const int t = threadIdx.x;
@@ -1195,11 +1185,8 @@ struct PairArgs {
                               // from the two-plane halo (ghost + far ghost planes, pft_slab_far)
   int k_begin, k_end, kz, ntile, nchunk, ntx;
   int kspan;            // planes a chunk runs from its start (kz; 2 for the two-plane boundary launch)
-  // inline boundary (PFT_K_INLINE, PFT_K_ENDS_FIRST): the grid's first nbw workgroups produce the
-  // planes the exchange sends, each adding one to *bdone once they are written back (nbw 0: none).
-  // bends 0: they run the two planes at each end (chunk 0: planes 0, 1; chunk 1: n3 - 2, n3 - 1)
-  // and the other nint workgroups the chunks of [k_begin, k_end); bends 1: one launch of the whole
-  // slab's chunks, the first and the last chunk of every tile column first, then chunks c0 ..
+  // inline boundary (PFT_K_INLINE, PFT_K_ENDS_FIRST; pft_zplan.h): the grid's first nbw workgroups
+  // produce the planes the exchange sends, each adding one to *bdone once they are written back
   int nbw, bends, c0, nint;
   unsigned long long* bdone;
   int tx, ty;           // R0 tile: tx cells (even) x ty rows
@@ -1501,12 +1488,9 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
   __shared__ unsigned lXa[PFT_PAIR_NEX];
 
   const int TX = a.tx, TY = a.ty, WP2 = TX / 2 + 2, NPOS = WP2 * (TY + 4);
-  // inline boundary: the leading workgroups (dispatched first) are the boundary chunks
-  const bool bw = (int)blockIdx.x < a.nbw;
-  const int lin = bw ? xcd_remap(blockIdx.x, a.nbw) : xcd_remap(blockIdx.x - a.nbw, a.nint);
-  const int tile = lin % a.ntile, cq = lin / a.ntile;
-  const int chunk = bw ? (a.bends ? (cq ? a.nchunk - 1 : 0) : cq) : a.c0 + cq;
-  const bool bshort = bw && !a.bends;   // a two-plane boundary chunk (PFT_K_INLINE)
+  int tile, chunk, kb, ke;
+  bool bw, bshort;
+  pft_zplan_chunk((int)blockIdx.x, a.ntile, a.nchunk, a.nbw, a.bends, a.c0, a.nint, &tile, &chunk, &bw, &bshort);
   const int x0 = (tile % a.ntx) * TX, y0 = (tile / a.ntx) * TY;
   // threads beyond the R2 positions shadow the last one (same loads and LDS writes, no stores)
   const int tt = min((int)threadIdx.x, NPOS - 1);
@@ -1574,8 +1558,7 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
     for (int q = 0; q < 3; ++q) LD::st(lA[slot][q], pe, pair_in_A<SA, GLX>(A, q, r));
   };
 
-  const int kb = bshort ? chunk * (a.n3 - 2) : a.k_begin + chunk * a.kz;
-  const int ke = bshort ? kb + 2 : min(kb + a.kspan, a.k_end);
+  pft_zplan_planes(chunk, bshort, a.n3, a.k_begin, a.k_end, a.kz, a.kspan, &kb, &ke);
   const int n3 = a.n3;
   const bool wlo = !a.has_below, whi = !a.has_above;         // walls (equation.c:164-183)
   // stage-A planes [mA0, mA1]: the chunk's planes and one on each side -- at a slab interface
@@ -2814,6 +2797,60 @@ static void launch_stage(int stage, int mode, int gls, int kind, dim3 g, hipStre
   });
 }
 
+// a launch's plan (slab_plan) into its kernel arguments (StageArgs, PairArgs) and into the record of
+// pft_slab_launch_geometry (rec 1..5: the stage the launch ends)
+template <class A>
+static void plan_apply(pft_slab* s, int rec, const pft_zplan& p, A& a)
+{
+  a.k_begin = p.k_begin;
+  a.k_end = p.k_end;
+  a.kz = p.kz;
+  a.kspan = p.kspan;
+  a.nchunk = p.nchunk;
+  a.nbw = p.nbw;
+  a.bends = p.bends;
+  a.c0 = p.c0;
+  a.nint = p.nint;
+  if (p.inl) a.bdone = s->bdone;
+  if (rec < 1) return;
+  s->launch_nwg[rec] = p.nbw + p.nint;
+  s->launch_kz[rec] = p.kz;
+  s->launch_ntile[rec] = a.ntile;
+  s->launch_bnd[rec] = p.bnd;
+}
+
+// a planned launch on its stream, with what follows it.  beside: a boundary launch on the boundary
+// stream, behind what the compute stream holds, so that it runs beside the interior launch.
+template <class F>
+static int launch_planned(pft_slab* s, const pft_zplan& p, bool beside, F&& launch)
+{
+  hipStream_t st = s->stream;
+  if (beside) {
+    HIPCHK(hipEventRecord(s->ev_pre, s->stream));
+    HIPCHK(hipStreamWaitEvent(s->bnd, s->ev_pre, 0));
+    st = s->bnd;
+  }
+  launch(st);
+  HIPCHK(hipGetLastError());
+  if (beside) {
+    HIPCHK(hipEventRecord(s->ev_bnd, s->bnd));
+    s->bnd_pending = 1;
+  }
+  if (p.inl) {
+    s->bdone_target += (unsigned long long)p.nbw;
+    s->inline_pending = 1;
+    // the copies' trigger, on the comm stream at once: queued now, it is normally dispatched while
+    // the previous launch still runs and sits on its CU before this launch fills the chip (pair 4+5
+    // at 256 VGPRs leaves no room beside its workgroups: a trigger queued later waited for a CU
+    // until this launch drained -- the copies then ran after it)
+    if (s->trig_early) {
+      bnd_trigger_kernel<<<1, 64, 0, s->comm>>>(s->bdone, s->bdone_target);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  return 0;
+}
+
 extern "C" {
 
 // merson_fused tile: wx cell pairs x ty rows, 256 threads.  Limits: wx * ty <= 256 threads, the
@@ -2866,49 +2903,29 @@ static double slab_fgeo(const pft_slab* cs, int* wx, int* ty)
   return s->fgeo_eff;
 }
 
-// z-chunk count memo: the cost models below scan every chunk count (400 planes: 400 candidates);
-// their result only depends on the occupancy, the tile count and the planes
-static int kz_memo_get(const pft_slab* s, int slot, long key)
+// z-chunk count memo: the cost model (pft_zplan_kz) scans every chunk count (400 planes: 400
+// candidates); its result only depends on its arguments, all of them in the key.  One slot per
+// launcher and chunking rule (plain, or ends-first's min_nch = 3): pft_slab::kz_memo.
+enum { KZ_STAGE = 0 /* + stage + 6 gls */, KZ_PAIR = 12 /* + (first == 4) */ };
+static int chunk_kz(void* memo, int occ, long ntile, int nplanes, int min_nch, int ncu)
 {
-  return s->kz_key[slot] == key + 1 ? s->kz_val[slot] : 0;
-}
-static void kz_memo_put(pft_slab* s, int slot, long key, int kz)
-{
-  s->kz_key[slot] = key + 1;
-  s->kz_val[slot] = kz;
+  pft_slab::KzMemo* m = (pft_slab::KzMemo*)memo + (min_nch >= 3 ? 1 : 0);
+  const long key = (((long)min_nch << 56) ^ ((long)occ << 52) ^ ((long)ncu << 40) ^ (ntile << 24) ^ (long)nplanes) + 1;
+  if (m->key != key) {
+    m->kz = pft_zplan_kz(occ, ntile, nplanes, min_nch, ncu);
+    m->key = key;
+  }
+  return m->kz;
 }
 
-// planes per z-chunk: a CU runs `occ` workgroups at a time; a chunk count with w = ceil(workgroups /
-// CUs) workgroups per CU costs (planes per chunk + the two planes a chunk re-reads) times
-//   - occ <= 2: ceil(w / occ) rounds -- a partial last round runs a CU at half its waves and the
-//     HBM-bound stages stall;
-//   - occ >= 3: max(1, w / occ) -- retiring workgroups are refilled at once, and the extra
-//     workgroups help the arithmetic-heavy stages hide latency.
-// The cheapest count wins (more chunks only when 5% cheaper).
-static int chunk_kz(pft_slab* s, int slot, int occ, long ntile, int nplanes, int min_nch = 1)
+// the plan of a launch (pft_zplan.h) on this slab: its forced kz, the compute stream's CUs (launches
+// on it chunk here) and the memo
+static int slab_plan(pft_slab* s, pft_zplan* p, int launcher, int k_begin, int k_end, int ntile, int occ,
+                     int depths, bool can_inline)
 {
-  const long key = ((long)occ << 52) ^ ((long)s->cu_reserved << 44) ^ (ntile << 24) ^ (long)nplanes;
-  int kz = kz_memo_get(s, slot, key);
-  if (kz) return kz;
-  int best_nch = 1;
-  double best_cost = -1.0;
-  if (min_nch > nplanes) min_nch = nplanes;
-  for (int nch = min_nch; nch <= nplanes; ++nch) {
-    const int k = (nplanes + nch - 1) / nch;
-    if (nch > min_nch && k == (nplanes + nch - 2) / (nch - 1)) continue;   // same kz as nch - 1
-    if ((nplanes + k - 1) / k < min_nch) continue;
-    if (min_nch >= 3 && (k < 2 || nplanes - ((nplanes + k - 1) / k - 1) * k < 2)) continue;   // edge chunks >= 2 planes
-    const long nb = ntile * ((nplanes + k - 1) / k);
-    const int ncu = s->n_cu - s->cu_reserved;   // the compute stream's CUs (launches on it chunk here)
-    const long per_cu = (nb + ncu - 1) / ncu;
-    const double rounds = occ <= 2 ? (double)((per_cu + occ - 1) / occ) : std::max(1.0, (double)per_cu / occ);
-    const double cost = rounds * (k + 2);
-    if (best_cost < 0.0 || cost < 0.95 * best_cost) { best_cost = cost; best_nch = nch; }
-  }
-  if (best_cost < 0.0) best_nch = std::max(1, nplanes);
-  kz = (nplanes + best_nch - 1) / best_nch;
-  kz_memo_put(s, slot, key, kz);
-  return kz;
+  const pft_zplan_in in = {k_begin, k_end, s->d.n3, ntile, s->kz, occ, s->n_cu - s->cu_reserved,
+                           depths, can_inline ? 1 : 0, chunk_kz, s->kz_memo[launcher]};
+  return pft_zplan_make(p, &in);
 }
 
 static int slab_kind(const pft_slab* s)
@@ -2983,10 +3000,15 @@ int pft_slab_stage_fields(const pft_slab* s, int stage)
   return 3;
 }
 
-// arm the deferred publication of an error-norm launch of nwg workgroups into host slot j: its
-// workgroups store partials (eps_store_part), the next stage-1 launch reduces and publishes them
-static int defer_arm(pft_slab* s, long nwg, int j, unsigned long long** part, long cap_nwg = 0)
+// arm the publication of an error-norm launch of nwg workgroups: the next slot of the host's ring
+// pre-set to the sentinel (here, before the launch; the host polls it in pft_slab_eps_fetch), and
+// the deferred publication into it -- the launch's workgroups store partials (eps_store_part), the
+// next stage-1 launch reduces and publishes them.  cap_nwg: partials to make room for now.
+static int pub_arm(pft_slab* s, long nwg, unsigned long long** part, long cap_nwg = 0)
 {
+  const int j = (int)(s->pub_next % PFT_PUB_SLOTS);
+  __atomic_store_n(&s->pub_ring[2 * j], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
+  __atomic_store_n(&s->pub_ring[2 * j + 1], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
   if (std::max(nwg, cap_nwg) > s->part_cap) {
     if (s->part) HIPCHK(hipFree(s->part));
     s->part = nullptr;
@@ -3006,24 +3028,6 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
 {
   const int mode = s->d.calc_mode;
   if (mode != 0 && mode != 1 && mode != 2 && mode != 10 && mode != 11) return -2;
-  // k_begin == PFT_K_BOUNDARY: the slab's two boundary planes (0 and n3 - 1) in ONE launch, two
-  // one-plane chunks n3 - 1 planes apart (what the z-neighbours need first)
-  const bool bnd = k_begin == PFT_K_BOUNDARY || k_begin == PFT_K_BOUNDARY2;
-  const int bdepth = k_begin == PFT_K_BOUNDARY2 ? 2 : 1;   // PFT_K_BOUNDARY2: planes 0, 1 and n3-2, n3-1
-  // inline boundary (merson_fused only, never gated): PFT_K_ENDS_FIRST -- the whole slab, the first
-  // and last chunk of every tile column leading -- or PFT_K_INLINE -- two-plane chunks at each end
-  // leading the interior [2, n3 - 2); ENDS_FIRST falls back to INLINE where the chunks cannot hold
-  // the two planes at each end
-  bool ends = k_begin == PFT_K_ENDS_FIRST;
-  const bool inl = k_begin == PFT_K_INLINE || ends;
-  if (inl && (kind != KFUSED || !s->bdone || s->d.n3 < 5 || s->gate_use_seq)) return -2;
-  if (bnd || inl) {
-    k_begin = 0;   // (inline: the planes are set below, once the chunking is known)
-    k_end = s->d.n3;
-  }
-  if (k_begin < 0) k_begin = 0;
-  if (k_end < 0 || k_end > s->d.n3) k_end = s->d.n3;
-  if (k_end <= k_begin) return 0;
   StageArgs a;
   memset(&a, 0, sizeof(a));
   a.in = in;
@@ -3036,7 +3040,6 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
   a.out = out;
   a.noise = s->noise;
   a.eps_bits = s->scratch;
-  a.shards = s->eps_shards + (bnd ? PFT_EPS_SHARDS : 0);
   a.nonfinite = (unsigned int*)(s->scratch + 1);
   a.fs = s->fs;
   a.n1 = s->d.n1;
@@ -3045,8 +3048,6 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
   a.plane = s->plane;
   a.has_below = s->d.has_below;
   a.has_above = s->d.has_above;
-  a.k_begin = k_begin;
-  a.k_end = k_end;
   // tile: tile_wx 1 / 2 = automatic (fused_geometry), else that many pairs per row
   const bool auto_tile = s->tile_wx == 1 || s->tile_wx == 2;
   if (kind == KFUSED) {
@@ -3061,54 +3062,20 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
   } else {
     a.ntile = (s->plane + PFT_BLOCK - 1) / PFT_BLOCK;
   }
-  if (ends) {
-    const int n3 = s->d.n3;
-    const int occ = stage_occupancy(stage, mode, gls, kind);
-    const int kz = s->kz > 0 ? s->kz : chunk_kz(s, 14, occ, a.ntile, n3, 3);
-    const int nch = (n3 + kz - 1) / kz;
-    if (kz < 2 || nch < 3 || n3 - (nch - 1) * kz < 2) ends = false;
-  }
-  if (inl) {
-    k_begin = ends ? 0 : 2;
-    k_end = ends ? s->d.n3 : s->d.n3 - 2;
-    a.k_begin = k_begin;
-    a.k_end = k_end;
-  }
-  const int nplanes = k_end - k_begin;
-  if (s->kz > 0) {
-    a.kz = s->kz;
-  } else if (ends) {
-    a.kz = chunk_kz(s, 14, stage_occupancy(stage, mode, gls, kind), a.ntile, nplanes, 3);
-  } else {
-    // automatic (chunk_kz)
-    // Measured at 400^3 (80 tiles):
-    // stage 5 (occ 2) 6 chunks, 0.348 ms vs 0.393 for 16; stage 1 (occ 3) 16 chunks of 25 planes,
-    // 0.153 vs 0.163 for 9 of 45.  On a 400 x 400 x 100 slab (320 tiles, one 800^3 8-way rank)
-    // stages 4-5: 3 chunks (960 workgroups, 2 rounds) 0.261 / 0.349 ms against 0.314 / 0.436 for
-    // one round of 320 (64 CUs with 2 workgroups, 192 with 1).
-    const int occ = stage_occupancy(stage, mode, gls, kind);
-    a.kz = chunk_kz(s, stage + 6 * (gls ? 1 : 0), occ, a.ntile, nplanes);
-  }
-  a.nchunk = (nplanes + a.kz - 1) / a.kz;
-  a.kspan = a.kz;
-  if (bnd) {
-    a.kz = std::max(1, s->d.n3 - bdepth);
-    a.kspan = bdepth;
-    a.nchunk = s->d.n3 > bdepth ? 2 : 1;
-  }
-  a.nint = a.ntile * a.nchunk;
-  if (inl) {
-    a.bdone = s->bdone;
-    if (ends) {
-      const int nb = std::min(a.nchunk, 2);
-      a.nbw = nb * a.ntile;
-      a.bends = 1;
-      a.c0 = 1;
-      a.nint = (a.nchunk - nb) * a.ntile;
-    } else {
-      a.nbw = 2 * a.ntile;
-    }
-  }
+  // the z-chunks.  Measured at 400^3 (80 tiles): stage 5 (occ 2) 6 chunks, 0.348 ms vs 0.393 for 16;
+  // stage 1 16 chunks of 25 planes, 0.153 ms vs 0.163 for 9 of 45 (the cost model's own choice for
+  // occ 3 is 9 of 45).  On a 400 x 400 x 100 slab (320 tiles, one 800^3 8-way rank) stages 4-5: 3
+  // chunks (960 workgroups, 2 rounds) 0.261 / 0.349 ms against 0.314 / 0.436 for one round of 320
+  // (64 CUs with 2 workgroups, 192 with 1).
+  // Boundary launches of either depth; the inline boundary is merson_fused's, never gated.
+  pft_zplan p;
+  const int prc = slab_plan(s, &p, KZ_STAGE + stage + 6 * (gls ? 1 : 0), k_begin, k_end, a.ntile,
+                            stage_occupancy(stage, mode, gls, kind), 1 | 2,
+                            kind == KFUSED && s->bdone && !s->gate_use_seq);
+  if (prc <= 0) return prc;
+  const bool bnd = p.bnd != 0;
+  plan_apply(s, stage, p, a);
+  a.shards = s->eps_shards + (bnd ? PFT_EPS_SHARDS : 0);
   a.T_top = t_stage < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
   a.coef = coef;
   a.h = h;
@@ -3131,25 +3098,14 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
   a.em1 = s->d.eps_mult[1];
   a.em2 = s->d.eps_mult[2];
   s->pub_armed = 0;
-  if (stage == 5 && kind == KFUSED && out && !bnd && k_begin == 0 && k_end == s->d.n3 && s->inkernel_pub) {
-    // the whole slab in one launch: its last workgroup publishes the error norm (slot pre-set to
-    // the sentinel here, before the launch; the host polls it in pft_slab_eps_fetch)
-    const int j = (int)(s->pub_next % PFT_PUB_SLOTS);
-    __atomic_store_n(&s->pub_ring[2 * j], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
-    __atomic_store_n(&s->pub_ring[2 * j + 1], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
-    const int rc = defer_arm(s, (long)a.ntile * a.nchunk, j, &a.part);
-    if (rc) return rc;
+  if (stage == 5 && kind == KFUSED && out && !bnd && p.k_begin == 0 && p.k_end == s->d.n3 && s->inkernel_pub) {
+    // the whole slab in one launch: its error norm is published for the host
+    if (int rc = pub_arm(s, (long)a.ntile * a.nchunk, &a.part)) return rc;
     s->pub_armed = 1;
-    s->pub_slot = j;
+    s->pub_slot = s->defer_slot;
   }
   dim3 g((unsigned)(a.nbw + a.nint));
-  if (stage >= 1) {
-    s->launch_nwg[stage] = a.nbw + a.nint;
-    s->launch_kz[stage] = a.kz;
-    s->launch_ntile[stage] = a.ntile;
-    s->launch_bnd[stage] = bnd ? 1 : 0;
-    if (stage == 5) s->launch_part = a.part != nullptr;
-  }
+  if (stage == 5) s->launch_part = a.part != nullptr;
   bool extra = false;
   // a stage launch's interior fills the chip: its boundary runs beside it only in bnd_mode 1 (slower:
   // the two launches' workgroups are dealt interleaved and the interior ends late).  In the boundary
@@ -3188,29 +3144,9 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
     extra = true;
   }
   if (extra) g.x += 1;
-  hipStream_t st = s->stream;
-  if (beside) {
-    HIPCHK(hipEventRecord(s->ev_pre, s->stream));
-    HIPCHK(hipStreamWaitEvent(s->bnd, s->ev_pre, 0));
-    st = s->bnd;
-  }
-  launch_stage(stage, mode, gls, kind, g, st, a, s->c);
-  HIPCHK(hipGetLastError());
-  if (beside) {
-    HIPCHK(hipEventRecord(s->ev_bnd, s->bnd));
-    s->bnd_pending = 1;
-  } else if (bnd) {
-    s->bnd_split = 1;   // a boundary launch before its interior on the compute stream
-  }
-  if (inl) {
-    // as run_pair: the copies' trigger queued with the launch
-    s->bdone_target += (unsigned long long)a.nbw;
-    s->inline_pending = 1;
-    if (s->trig_early) {
-      bnd_trigger_kernel<<<1, 64, 0, s->comm>>>(s->bdone, s->bdone_target);
-      HIPCHK(hipGetLastError());
-    }
-  }
+  if (int rc = launch_planned(s, p, beside, [&](hipStream_t st) { launch_stage(stage, mode, gls, kind, g, st, a, s->c); }))
+    return rc;
+  if (bnd && !beside) s->bnd_split = 1;   // a boundary launch before its interior on the compute stream
   return 0;
 }
 
@@ -3873,73 +3809,21 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
   a.plane = s->plane;
   a.has_below = s->d.has_below;
   a.has_above = s->d.has_above;
-  // k_begin == PFT_K_BOUNDARY2: planes 0, 1 and n3-2, n3-1 in one launch (two 2-plane chunks);
-  // PFT_K_INLINE: those chunks first, then the interior [2, n3 - 2), in one launch (bnd_mode 4)
-  const bool bnd = k_begin == PFT_K_BOUNDARY2;
-  bool ends = k_begin == PFT_K_ENDS_FIRST;
-  const bool inl = k_begin == PFT_K_INLINE || ends;
-  if (ends) {
-    // the first and the last chunk must hold the two planes at each end (kz >= 2, a last chunk of
-    // two planes or more) and leave a chunk between them; otherwise the two-plane boundary chunks
-    const int n3 = s->d.n3;
-    const int occ = pair_occupancy(first, mode);
-    const int kz = s->kz > 0 ? s->kz : chunk_kz(s, 14 + (first == 4 ? 1 : 0), occ, s->pair_ntile, n3, 3);
-    const int nch = (n3 + kz - 1) / kz;
-    if (kz < 2 || nch < 3 || n3 - (nch - 1) * kz < 2) ends = false;
-  }
-  if (inl && (!s->bdone || s->d.n3 < 5)) return -2;
-  a.shards = s->eps_shards + (bnd ? PFT_EPS_SHARDS : 0);
-  if (inl) {
-    k_begin = ends ? 0 : 2;
-    k_end = ends ? s->d.n3 : s->d.n3 - 2;
-  }
-  if (bnd || k_begin < 0) k_begin = 0;
-  if (bnd || k_end < 0 || k_end > s->d.n3) k_end = s->d.n3;
-  if (k_end <= k_begin) return 0;
-  a.k_begin = k_begin;
-  a.k_end = k_end;
   a.tx = s->pair_tx;
   a.ty = s->pair_ty;
   if (s->pair_ntile <= 0 || !pair_geometry_ok(a.tx, a.ty)) return -2;
   a.ntx = (a.n1 + a.tx - 1) / a.tx;
   a.ntile = a.ntx * ((a.n2 + a.ty - 1) / a.ty);
-  const int nplanes = k_end - k_begin;
-  if (s->kz > 0) {
-    a.kz = s->kz;
-  } else {
-    // z-chunks as run_stage's cost model: a chunk of kz planes evaluates stage A on kz + 2 and
-    // loads kz + 3; `occ` workgroups per CU (one: 141 KiB of LDS)
-    const int occ = pair_occupancy(first, mode);
-    // end chunks first: at least three chunks, so that the first and last of a column are done
-    // while the others still run (the exchange's copies go beside them)
-    a.kz = chunk_kz(s, (ends ? 14 : 12) + (first == 4 ? 1 : 0), occ, a.ntile, nplanes, ends ? 3 : 1);
-  }
-  a.nchunk = (nplanes + a.kz - 1) / a.kz;
-  a.kspan = a.kz;
-  a.nint = a.ntile * a.nchunk;
-  if (bnd) {
-    a.kz = std::max(1, s->d.n3 - 2);
-    a.kspan = 2;
-    a.nchunk = s->d.n3 > 2 ? 2 : 1;
-    a.nint = a.ntile * a.nchunk;
-  }
-  if (inl) {
-    a.bdone = s->bdone;
-    if (ends) {
-      const int nb = std::min(a.nchunk, 2);
-      a.nbw = nb * a.ntile;
-      a.bends = 1;
-      a.c0 = 1;
-      a.nint = (a.nchunk - nb) * a.ntile;
-    } else {
-      a.nbw = 2 * a.ntile;
-    }
-  }
+  // z-chunks by run_stage's cost model: a chunk of kz planes evaluates stage A on kz + 2 and loads
+  // kz + 3; `occ` workgroups per CU (one: 141 KiB of LDS).  The boundary launch is the two-plane one.
+  pft_zplan p;
+  const int prc = slab_plan(s, &p, KZ_PAIR + (first == 4 ? 1 : 0), k_begin, k_end, a.ntile, pair_occupancy(first, mode), 2,
+                            s->bdone != nullptr);
+  if (prc <= 0) return prc;
+  const bool bnd = p.bnd != 0, inl = p.inl != 0;
+  plan_apply(s, first + 1, p, a);
+  a.shards = s->eps_shards + (bnd ? PFT_EPS_SHARDS : 0);
   const long nwg = (long)a.nbw + (long)a.nint;   // the launch's workgroups
-  s->launch_nwg[first + 1] = (int)nwg;
-  s->launch_kz[first + 1] = a.kz;
-  s->launch_ntile[first + 1] = a.ntile;
-  s->launch_bnd[first + 1] = bnd ? 1 : 0;
   a.T_topA = t_a < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
   a.T_topB = t_b < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
   // exactly the solver's h/3.0, h/6.0 and h/8.0 (and run_stage's stage-input coefficients)
@@ -3957,23 +3841,15 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
   s->pub_armed = 0;
   const int split_pub = s->split_pub;
   s->split_pub = 0;
-  if (first == 4 && s->inkernel_pub && !bnd && ((k_begin == 0 && k_end == s->d.n3) || inl)) {
-    const int j = (int)(s->pub_next % PFT_PUB_SLOTS);
-    __atomic_store_n(&s->pub_ring[2 * j], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
-    __atomic_store_n(&s->pub_ring[2 * j + 1], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
-    const int rc = defer_arm(s, nwg, j, &a.part);
-    if (rc) return rc;
+  if (first == 4 && s->inkernel_pub && !bnd && ((p.k_begin == 0 && p.k_end == s->d.n3) || inl)) {
+    if (int rc = pub_arm(s, nwg, &a.part)) return rc;
     s->pub_armed = 1;
-    s->pub_slot = j;
+    s->pub_slot = s->defer_slot;
   } else if (first == 4 && s->inkernel_pub && bnd) {
     // split stage 4+5 (boundary, then interior: rk_solver do_pair): the boundary launch's partials
     // first, the interior's after them (the capacity for both now: no reallocation between the two
     // launches), reduced and published by the next stage-1 launch as for one launch
-    const int j = (int)(s->pub_next % PFT_PUB_SLOTS);
-    __atomic_store_n(&s->pub_ring[2 * j], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
-    __atomic_store_n(&s->pub_ring[2 * j + 1], PFT_PUB_SENTINEL, __ATOMIC_RELEASE);
-    const int rc = defer_arm(s, (long)a.ntile * a.nchunk, j, &a.part, (long)a.ntile * (a.nchunk + s->d.n3));
-    if (rc) return rc;
+    if (int rc = pub_arm(s, (long)a.ntile * a.nchunk, &a.part, (long)a.ntile * (a.nchunk + s->d.n3))) return rc;
     s->split_pub = 1;
   } else if (first == 4 && split_pub && !bnd && s->defer_n > 0 &&
              s->defer_n + (long)a.ntile * a.nchunk <= s->part_cap) {
@@ -3984,38 +3860,15 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
   }
   if (first == 4) s->launch_part = a.part != nullptr;
   const dim3 g((unsigned)nwg);
-  hipStream_t st = s->stream;
   // bnd_mode 1, 2: the boundary launch beside the interior one.  On a 400 x 400 plane the interior
   // holds one workgroup per tile column, 220 of 256 CUs: the boundary's workgroups take the CUs it
   // leaves and the copies start while the interior still runs.  An interior launch of more
   // workgroups than CUs (several rounds, the 318^2 and 252^2 planes) leaves CUs only in its last
-  // round, and beside is still no slower there than before (profiles/r05_ce_shapes.txt)
+  // round, and beside is still no slower there than before (profiles/r05_ce_shapes.txt).  (Not so
+  // a stage launch's boundary, whose interior fills the chip: run_stage, mode 1 only)
   const bool beside = bnd && s->bnd_mode != 0;
-  if (beside) {
-    HIPCHK(hipEventRecord(s->ev_pre, s->stream));
-    HIPCHK(hipStreamWaitEvent(s->bnd, s->ev_pre, 0));
-    st = s->bnd;
-  }
   const int lwp = pair_lwp(a.tx);
-  launch_pair(first, mode, glx, lwp, g, st, a, s->c);
-  HIPCHK(hipGetLastError());
-  if (beside) {
-    HIPCHK(hipEventRecord(s->ev_bnd, s->bnd));
-    s->bnd_pending = 1;
-  }
-  if (inl) {
-    s->bdone_target += (unsigned long long)a.nbw;
-    s->inline_pending = 1;
-    // the copies' trigger, on the comm stream at once: queued now, it is normally dispatched while
-    // the previous launch still runs and sits on its CU before this launch fills the chip (pair 4+5
-    // at 256 VGPRs leaves no room beside its workgroups: a trigger queued later waited for a CU
-    // until this launch drained -- the copies then ran after it)
-    if (s->trig_early) {
-      bnd_trigger_kernel<<<1, 64, 0, s->comm>>>(s->bdone, s->bdone_target);
-      HIPCHK(hipGetLastError());
-    }
-  }
-  return 0;
+  return launch_planned(s, p, beside, [&](hipStream_t st) { launch_pair(first, mode, glx, lwp, g, st, a, s->c); });
 }
 
 extern "C" {

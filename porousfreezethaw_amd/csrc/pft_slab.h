@@ -145,8 +145,10 @@ struct pft_slab {
   // host-side memos (a small slab is host-bound: ~5 launches of a few us per attempted step)
   int fgeo_valid, fgeo_wx, fgeo_ty;  // fused_geometry(n1, n2) of this slab
   double fgeo_eff;
-  long kz_key[16];                   // z-chunk cost model: key (occupancy, tiles, planes) -> kz
-  int kz_val[16];
+  struct KzMemo {                    // z-chunk cost model memo (chunk_kz): key (its arguments) -> kz,
+    long key;                        // per launcher (KZ_*) and chunking rule (plain, ends-first)
+    int kz;
+  } kz_memo[14][2];
   int launch_nwg[6], launch_kz[6], launch_ntile[6];   // the last launch that ended stage 1..5 (pft_slab_launch_geometry)
   int launch_bnd[6];                 // ... and whether it was the boundary launch of a split stage
   int launch_part;                   // ... and whether the last error-norm launch stored deferred partials

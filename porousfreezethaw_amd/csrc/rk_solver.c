@@ -252,112 +252,77 @@ static int canonical_chunks(const RK_MEM_DIST * n, double em[3])
 	return R.max_n >= PFT_VAR_COUNT*S;
 }
 
-/* one stage of the step on this slab; stage 6 = the speculative stage 1 of the next step
-   (K1' = f(ts, XN) into A1, pft_slab_stage_spec) */
-static int run1(int stage, double ts, double coef, double h, int kb, int ke)
+/* what place() launches: one stage of the step on this slab (stage 1..5; 6 = the speculative stage 1
+   of the next step, K1' = f(ts, XN) into A1, pft_slab_stage_spec), or stages first, first+1 (2+3 or
+   4+5) as ONE pair kernel (pft_slab_pair; stage times ts, tb) */
+typedef struct {
+	int stage, first;
+	double ts, tb, coef, h;
+} launch_what;
+
+static int run1(const launch_what * w, int kb, int ke)
 {
-	return stage == 6 ? pft_slab_stage_spec(R.slab, ts, kb, ke) : pft_slab_stage(R.slab, stage, ts, coef, h, kb, ke);
+	if(w->first) return pft_slab_pair_range(R.slab, w->first, w->ts, w->tb, w->h, w->coef, kb, ke);
+	return w->stage == 6 ? pft_slab_stage_spec(R.slab, w->ts, kb, ke)
+	                     : pft_slab_stage(R.slab, w->stage, w->ts, w->coef, w->h, kb, ke);
+}
+
+/* a launch and the exchange of its output's boundary planes (nfields fields of out_buf), timed as
+   stage tstage */
+static int place(const launch_what * w, int out_buf, int nfields, int tstage, long * launches)
+{
+	pft_comm * c = comm();
+	/* boundary first: the transport splits, and is not ipc with put kernels */
+	const int n3 = R.slab_grid.n3, bf = pft_comm_boundary_first(c);
+	int rc, depth = 0, inl = 0;   /* planes at each end of a split launch's boundary; an inline boundary's code */
+	if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 0);
+	if(R.deep && bf && n3 >= 5) {
+		/* pair path between slabs over RCCL or the copy engines: the output's two-plane halo (the next
+		   pair kernel evaluates its stage A on the ghost planes too; K3, or x(t+h): gl only where
+		   stored) -- the two planes at each end first, their exchange on the comm stream beside the
+		   interior launch, which reads no ghost plane; or (inl) one launch whose leading workgroups
+		   produce those planes, the copies starting when they are done (PFT_K_INLINE, PFT_K_ENDS_FIRST) */
+		depth = 2;
+		inl = w->first ? pft_slab_pair_inline(R.slab, w->first) : pft_slab_stage_inline(R.slab);
+	} else if(!R.deep && !w->first && bf) {
+		/* SURVEY 8e.  Stage s reads the stage-(s-1) values of planes -1..n3 and writes its own; only
+		   its two boundary planes read ghost planes: they are launched first, exchanged on the comm
+		   stream beside the interior sweep, and the compute stream waits for the exchange before the
+		   next stage.  (Measured slower and removed: the boundary launch on the comm stream with the
+		   interior sweep waiting for it, and two-stream orders) */
+		depth = 1;
+	}
+	if(depth) {
+		*launches += inl ? 1 : 2;
+		if((rc = run1(w, inl ? inl : depth == 2 ? PFT_K_BOUNDARY2 : PFT_K_BOUNDARY, 0))) return rc;
+		if((rc = depth == 2 ? pft_comm_halo_start_deep(c, out_buf, 0, nfields) : pft_comm_halo_start(c, out_buf, 0, nfields)))
+			return rc;
+		if(!inl && n3 > 2*depth && (rc = run1(w, depth, n3-depth))) return rc;   /* (depth 2: n3 >= 5) */
+		if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
+		return pft_comm_halo_finish(c);
+	}
+	(*launches)++;
+	if((rc = run1(w, -1, -1))) return rc;
+	if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
+	/* ... then, between slabs with put kernels (ipc), stream-ordered: the boundary planes into the
+	   neighbours' ghost planes and the wait for theirs in ours (pair path: the two-plane halo) */
+	if(R.deep) return pft_comm_halo_deep(c, out_buf, 0, nfields);
+	if(!w->first && pft_comm_device_halo(c) && !bf) return pft_comm_halo(c, out_buf, 0, nfields);
+	return 0;
 }
 
 static int do_stage(int stage, double ts, double coef, double h, long * launches)
 {
-	pft_comm * c = comm();
-	const int out_buf = stage == 6 ? PFT_BUF_A1 : pft_slab_stage_output(R.slab, stage);
-	const int nfields = pft_slab_stage_fields(R.slab, stage);
-	const int tstage = stage == 6 ? 1 : stage;
-	int rc, n3;
-	if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 0);
-	if(R.deep) {
-		/* pair path between slabs: the output's two-plane halo (the next pair kernel evaluates its
-		   stage A on the ghost planes too).  RCCL and ipc on the copy engines: the two planes at each
-		   end first, their exchange on the comm stream beside the interior launch; ipc with put
-		   kernels: the whole slab, then the put. */
-		n3 = R.slab_grid.n3;
-		if(pft_comm_boundary_first(c) && n3 >= 5 && (rc = pft_slab_stage_inline(R.slab))) {
-			/* one launch whose leading workgroups produce the planes the exchange sends (as do_pair) */
-			if((rc = run1(stage, ts, coef, h, rc, 0))) return rc;
-			if((rc = pft_comm_halo_start_deep(c, out_buf, 0, nfields))) return rc;
-			if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
-			(*launches)++;
-			return pft_comm_halo_finish(c);
-		}
-		if(pft_comm_boundary_first(c) && n3 >= 5) {
-			if((rc = run1(stage, ts, coef, h, PFT_K_BOUNDARY2, 0))) return rc;
-			if((rc = pft_comm_halo_start_deep(c, out_buf, 0, nfields))) return rc;
-			if((rc = run1(stage, ts, coef, h, 2, n3-2))) return rc;
-			if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
-			*launches += 2;
-			return pft_comm_halo_finish(c);
-		}
-		(*launches)++;
-		if((rc = run1(stage, ts, coef, h, -1, -1))) return rc;
-		if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
-		return pft_comm_halo_deep(c, out_buf, 0, nfields);
-	}
-	if(pft_comm_device_halo(c) && !pft_comm_boundary_first(c)) {
-		/* ipc: the whole slab in one launch, then (stream-ordered) the boundary planes into the
-		   neighbours' ghost planes and the wait for theirs in ours */
-		(*launches)++;
-		if((rc = run1(stage, ts, coef, h, -1, -1))) return rc;
-		if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
-		return pft_comm_halo(c, out_buf, 0, nfields);
-	}
-	if(!pft_comm_splits(c)) {
-		(*launches)++;
-		rc = run1(stage, ts, coef, h, -1, -1);
-		if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
-		return rc;
-	}
-	/* SURVEY 8e.  Stage s reads the stage-(s-1) values of planes -1..n3 and writes its own; only
-	   its two boundary planes read ghost planes: they are launched first, exchanged on the comm
-	   stream beside the interior sweep, and the compute stream waits for the exchange before the
-	   next stage.  (Measured slower and removed: the boundary launch on the comm stream with the
-	   interior sweep waiting for it, and two-stream orders) */
-	n3 = R.slab_grid.n3;
-	if((rc = run1(stage, ts, coef, h, PFT_K_BOUNDARY, 0))) return rc;
-	if((rc = pft_comm_halo_start(c, out_buf, 0, nfields))) return rc;
-	if(n3 > 2 && (rc = run1(stage, ts, coef, h, 1, n3-1))) return rc;
-	if(R.tstep) pft_slab_timing_mark(R.slab, tstage, 1);
-	*launches += 2;
-	return pft_comm_halo_finish(c);
+	const launch_what w = {stage, 0, ts, 0.0, coef, h};
+	return place(&w, stage == 6 ? PFT_BUF_A1 : pft_slab_stage_output(R.slab, stage),
+	             pft_slab_stage_fields(R.slab, stage), stage == 6 ? 1 : stage, launches);
 }
 
-/* stages first, first+1 (2+3 or 4+5) of the step as ONE pair kernel (pft_slab_pair; one slab):
-   timed as stage first+1 */
+/* timed as stage first+1 */
 static int do_pair(int first, double ta, double tb, double h, double coef, long * launches)
 {
-	pft_comm * c = comm();
-	const int out_buf = first == 2 ? PFT_BUF_K3 : PFT_BUF_XN, n3 = R.slab_grid.n3;
-	int rc;
-	if(R.tstep) pft_slab_timing_mark(R.slab, first+1, 0);
-	if(R.deep && pft_comm_boundary_first(c) && n3 >= 5) {
-		/* between slabs over RCCL or the copy engines: the two planes at each end first, their
-		   exchange (K3, or x(t+h): gl only where stored) beside the interior launch, which reads no
-		   ghost plane */
-		const int nf = pft_slab_stage_fields(R.slab, first+1);
-		const int inl = pft_slab_pair_inline(R.slab, first);
-		if(inl) {
-			/* one launch whose leading workgroups produce the planes the exchange sends; the copies
-			   start when they are done (PFT_K_INLINE, PFT_K_ENDS_FIRST) */
-			(*launches)++;
-			if((rc = pft_slab_pair_range(R.slab, first, ta, tb, h, coef, inl, 0))) return rc;
-			if((rc = pft_comm_halo_start_deep(c, out_buf, 0, nf))) return rc;
-			if(R.tstep) pft_slab_timing_mark(R.slab, first+1, 1);
-			return pft_comm_halo_finish(c);
-		}
-		*launches += 2;
-		if((rc = pft_slab_pair_range(R.slab, first, ta, tb, h, coef, PFT_K_BOUNDARY2, 0))) return rc;
-		if((rc = pft_comm_halo_start_deep(c, out_buf, 0, nf))) return rc;
-		if((rc = pft_slab_pair_range(R.slab, first, ta, tb, h, coef, 2, n3-2))) return rc;
-		if(R.tstep) pft_slab_timing_mark(R.slab, first+1, 1);
-		return pft_comm_halo_finish(c);
-	}
-	(*launches)++;
-	rc = pft_slab_pair(R.slab, first, ta, tb, h, coef);
-	if(R.tstep) pft_slab_timing_mark(R.slab, first+1, 1);
-	if(rc || !R.deep) return rc;
-	/* between slabs (ipc): the whole slab, then the two-plane halo */
-	return pft_comm_halo_deep(c, out_buf, 0, pft_slab_stage_fields(R.slab, first+1));
+	const launch_what w = {0, first, ta, tb, coef, h};
+	return place(&w, first == 2 ? PFT_BUF_K3 : PFT_BUF_XN, pft_slab_stage_fields(R.slab, first+1), first+1, launches);
 }
 
 /* gl evolves by dgl == 0 (equation.c:731,874), so x(t+h) of gl is x + coef*0.0: x itself, bit for

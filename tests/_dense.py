@@ -93,7 +93,8 @@ ATTEMPTS = 6
 # 40 x 20 pair tile 3 x 3 times and the automatic fused tile (42 x 12) 3 x 5 times, each with an
 # interior tile.  The golden grid, 44 x 24: 3 pair tiles of 16 x 24, 2 x 2 fused16 tiles, 1 x 3
 # fused32 tiles; its "default" flavour is the cache kernel, on the grids here the automatic fused one.
-GRIDS = [(66, 38, 7), (130, 70, 5), (120, 60, 6)]
+# The last three: the golden grid's plane, 5, 6 and 7 planes (tests/test_zplan_gpu.py).
+GRIDS = [(66, 38, 7), (130, 70, 5), (120, 60, 6), (44, 24, 5), (44, 24, 6), (44, 24, 7)]
 
 _cache = {}
 
