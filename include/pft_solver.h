@@ -13,6 +13,7 @@
 #include "pft_hip.h"
 #include "pft_formula.h"
 #include "pft_hist.h"
+#include "pft_map.h"
 #include "pft_io.h"
 
 #ifdef __cplusplus
@@ -94,6 +95,29 @@ int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, cons
                     int nbins, const double * edges, pft_hist_head * global, long long * global_counts,
                     pft_hist_head * local, long long * local_counts, pft_hist_head * plane_heads,
                     long long * plane_counts);
+
+/* f15: the map (pft_map.h) of a formula's values over the cells a mask formula selects, reduced along
+   `axis` (0 z, 1 y, 2 x: numpy's numbering of the interior [k][j][i]), of the device-resident x,
+   under the rules of pft_solver_hist word for word: valid after any fused solve or device IC, -3
+   without an initialised solver or a resident state (never stale numbers), 0 from a
+   Service_Callback on one rank and -2 there with several.  The value: nv entries in vops / vargs
+   (pft_frontend.h); the mask: nm entries in mops / margs, or 0, NULL, NULL for none.  Every rank
+   compiles first (pft_formula_compile) and the ranks agree the outcome before any device work: 1
+   when a program is not device-exact (nothing is launched: use pft_map_host), -2 for a bad program,
+   a bad axis or limits exceeded, the same on every rank.  That first pft_comm_allgather round also
+   carries a 64-bit hash of the axis, of whether `global` is given and of both programs: ranks that
+   were given different maps all return -2, before any device work.
+   local (required): this slab's map, pft_map_dims records (pft_slab_map).  For axes 1 and 2 these
+   are the slab's own rows first_row .. first_row + n3 - 1 of the whole grid's map, and complete;
+   for axis 0 it is the slab's partial map, with first / last as global z indices.
+   global (optional): the whole grid's map, the same bits on every rank: n2 x n1 records for axis 0
+   (the ranks' partial maps combined in rank order), total_n3 x n1 or total_n3 x n2 for axes 1 and 2
+   (the ranks' rows put together; every rank sends as many rows as the tallest slab has, the rest
+   neutral).  It travels with the rank's status by pft_comm_allgather_any, 256 bytes per rank and
+   round: a 200 x 200 map takes about 8 750 rounds (has the measured
+   time); NULL skips it, and only the statuses travel.  A single rank makes no collective. */
+int pft_solver_map(int nv, const int * vops, const double * vargs, int nm, const int * mops, const double * margs,
+                   int axis, pft_map_px * global, pft_map_px * local);
 
 /* f1 (after RK_MPI_SA_init): the default Params' initial condition (Params:9-21,
    intertrack.c:1880-2010) and, with with_beads, the glass beads (PrecalculateData,

@@ -342,6 +342,37 @@ def write_hist_txt(rows, path, key):
             f.write(" ".join(str(int(c)) for c in r[key]) + "\n")
 
 
+MAP_KEYS = ("selected", "nonzero", "nonfinite", "min", "max", "first", "last")   # include/pft_map.h
+
+
+class pft_map_px(C.Structure):
+    """include/pft_map.h: one pixel of a map (f15), 56 bytes"""
+    _fields_ = [("selected", C.c_longlong), ("nonzero", C.c_longlong), ("nonfinite", C.c_longlong),
+                ("min", C.c_double), ("max", C.c_double), ("first", C.c_longlong), ("last", C.c_longlong)]
+
+
+MAP_DTYPE = np.dtype([(k, "<f8" if k in ("min", "max") else "<i8") for k in MAP_KEYS])   # pft_map_px as numpy sees it
+
+
+def map_spec(formula, axis, mask=None, variables=None):
+    """A map compiled for Simulation.project / run_series: the axis (0 z, 1 y, 2 x -- numpy's
+    numbering of interior()'s [k, j, i]) and the postfix programs of the value formula and of the
+    optional mask formula (formula_programs; its `variables`).  ValueError before any work for an
+    axis outside 0..2, an undefined symbol or a syntax error."""
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not 0 <= int(axis) <= 2:
+        raise ValueError(f"project: axis must be 0 (z), 1 (y) or 2 (x), not {axis!r}")
+    value = formula_programs({"formula": formula}, variables)
+    masked = None if mask is None else formula_programs({"mask": mask}, variables)
+    if masked is not None and len(value[2]) + len(masked[2]) > PFT_FORMULA_MAX_ENTRIES:
+        raise ValueError(f"project: formula and mask together have more than {PFT_FORMULA_MAX_ENTRIES} entries")
+    return {"compiled": True, "formula": str(formula), "mask": None if mask is None else str(mask), "axis": int(axis),
+            "value": value, "masked": masked}
+
+
+def _map_ptr(a):
+    return a.ctypes.data_as(C.POINTER(pft_map_px))
+
+
 class pft_ic_prog(C.Structure):
     """include/pft_frontend.h: a program compiled for the device (owned by the library: pft_ic_prog_free)"""
     _fields_ = [("n", C.c_int), ("op", C.POINTER(C.c_int)), ("arg", C.POINTER(C.c_double)), ("ntab", C.c_int),
@@ -469,6 +500,16 @@ def lib():
         L.pft_slab_hist_timing.argtypes = [C.c_void_p, C.c_int]
         L.pft_slab_hist_last_ms.argtypes = [C.c_void_p, dp]
         L.pft_solver_hist.argtypes = [C.c_int, ip, dp, C.c_int, ip, dp, C.c_int, dp, hp, llp, hp, llp, hp, llp]
+        mp = C.POINTER(pft_map_px)
+        L.pft_map_init.argtypes = [mp]
+        L.pft_map_init.restype = None
+        L.pft_map_combine.argtypes = [C.c_long, mp, mp]
+        L.pft_map_dims.argtypes = [gp, C.c_int, ip, ip]
+        L.pft_map_host.argtypes = [gp, dp, hpp, hpp, C.c_int, mp]
+        L.pft_slab_map.argtypes = [C.c_void_p, C.c_int, icp, icp, C.c_int, mp]
+        L.pft_slab_map_timing.argtypes = [C.c_void_p, C.c_int]
+        L.pft_slab_map_last_ms.argtypes = [C.c_void_p, dp]
+        L.pft_solver_map.argtypes = [C.c_int, ip, dp, C.c_int, ip, dp, C.c_int, mp, mp]
         rp, vpp = C.POINTER(pft_snapshot_ranges), C.POINTER(C.c_void_p)
         L.pft_snapshot_image_bytes.argtypes = [gp]
         L.pft_snapshot_image_bytes.restype = C.c_size_t
@@ -1103,6 +1144,117 @@ class Simulation:
             d["local"] = as_dict(lhead, lcounts)
         return d
 
+    # -- f15: 2-D maps of formula values --------------------------------------------------------------
+    def _map_neutral(self, n):
+        a = np.zeros(n, dtype=MAP_DTYPE)
+        a["min"], a["max"], a["first"], a["last"] = np.inf, -np.inf, -1, -1
+        return a
+
+    def _map_host_local(self, spec):
+        """pft_map_host of self.x: this slab's records, flat"""
+        _, _, vops, vargs = spec["value"]
+        value = pft_hist_prog(len(vops), _ip(vops), _dp(vargs))
+        mask = None
+        if spec["masked"] is not None:
+            _, _, mops, margs = spec["masked"]
+            mask = C.byref(pft_hist_prog(len(mops), _ip(mops), _dp(margs)))
+        rows, cols = self._map_dims(spec["axis"])
+        out = np.empty(rows * cols, dtype=MAP_DTYPE)
+        rc = self.lib.pft_map_host(C.byref(self.grid), _dp(self.x), C.byref(value), mask, spec["axis"], _map_ptr(out))
+        if rc:
+            raise RuntimeError(f"pft_map_host failed ({rc})")
+        return out
+
+    def _map_dims(self, axis):
+        rows, cols = C.c_int(), C.c_int()
+        if self.lib.pft_map_dims(C.byref(self.grid), axis, C.byref(rows), C.byref(cols)):
+            raise ValueError(f"project: pft_map_dims refused axis {axis!r} (-2)")
+        return rows.value, cols.value
+
+    def _map_host_global(self, spec, local):
+        """the ranks' host maps put together in rank order (collective), as pft_solver_map does it"""
+        g, axis = self.grid, spec["axis"]
+        rows, cols = self._map_dims(axis)
+        if axis == 0:
+            parts = self._gather_bytes(local.tobytes())
+            glob = np.frombuffer(parts[0], dtype=MAP_DTYPE).copy()
+            for part in parts[1:]:
+                other = np.frombuffer(part, dtype=MAP_DTYPE).copy()
+                self.lib.pft_map_combine(glob.size, _map_ptr(glob), _map_ptr(other))
+            return glob
+        places = [np.frombuffer(b, dtype=np.int64) for b in
+                  self._gather_bytes(np.array([g.first_row, g.n3], dtype=np.int64).tobytes())]
+        tallest = max(int(pl[1]) for pl in places)
+        mine = self._map_neutral(tallest * cols)
+        mine[:local.size] = local
+        glob = self._map_neutral(g.total_n3 * cols)
+        for pl, part in zip(places, self._gather_bytes(mine.tobytes())):
+            at, n = int(pl[0]) * cols, int(pl[1]) * cols
+            glob[at:at + n] = np.frombuffer(part, dtype=MAP_DTYPE)[:n]
+        return glob
+
+    def project(self, formula, axis, mask=None, variables=None, where="device", combine=True):
+        """f15: a formula of the parameter file's language (see formulas()) reduced along one axis of
+        the grid into a 2-D map (include/pft_map.h).  axis numbers interior()'s [k, j, i] as numpy
+        does: 0 reduces z (the map is [n2, n1]), 1 reduces y ([total_n3, n1]), 2 reduces x
+        ([total_n3, n2]).  Only the cells that the formula `mask` selects enter (value != 0, so a NaN
+        selects; a math error does not; None: every cell).  Returns a dict of 2-D arrays: selected,
+        nonzero (value != 0; a NaN counts), nonfinite (int64), min, max (float64, over the selected
+        values that are not NaN; +inf / -inf where there is none), first, last (int64: the global
+        index along the reduced axis of the first / last selected cell whose value is != 0, -1 where
+        there is none); and "axis" and "rows" = (first_row, n3), the z range of the grid that the map
+        covers.  With "p>0.5" along z, last is the front's height map and nonzero the ice thickness
+        in cells.  Integers and ordered extrema only: the same bits on any decomposition.
+        where="device": of the device-resident state, by pft_solver_map -- no download; collective
+        on several ranks; RuntimeError when nothing is resident; ValueError naming the formula when
+        the formula or the mask is not device-exact (use where="host").  where="host": pft_map_host
+        of self.x, put together over the ranks (collective too); it accepts every formula.
+        combine=False on several ranks: this slab's share alone -- its own rows for axes 1 and 2, its
+        partial map for axis 0 -- and no map crosses between the ranks.  ValueError before any work
+        for a bad axis, an undefined symbol or a syntax error."""
+        return self._answer("project", where,
+                            lambda: self._project(map_spec(formula, axis, mask, variables), where, combine))
+
+    def _project(self, spec, where, combine=True):
+        """project() on a compiled spec (map_spec); None when where="device" and nothing is resident
+        (pft_solver_map's -3, the same on every rank)"""
+        g, axis = self.grid, spec["axis"]
+        rows, cols = self._map_dims(axis)
+        comm = self.lib.pft_comm_current()
+        several = bool(comm) and self.lib.pft_comm_size(comm) > 1
+        glob = None
+        if where == "host":
+            local = self._map_host_local(spec)
+            if several and combine:
+                glob = self._map_host_global(spec, local)
+        else:
+            _, _, vops, vargs = spec["value"]
+            nm, mops, margs = 0, None, None
+            if spec["masked"] is not None:
+                _, _, mo, ma = spec["masked"]
+                nm, mops, margs = len(mo), _ip(mo), _dp(ma)
+            local = np.empty(rows * cols, dtype=MAP_DTYPE)
+            if several and combine:
+                glob = np.empty((rows if axis == 0 else g.total_n3) * cols, dtype=MAP_DTYPE)
+            rc = self.lib.pft_solver_map(len(vops), _ip(vops), _dp(vargs), nm, mops, margs, axis,
+                                         None if glob is None else _map_ptr(glob), _map_ptr(local))
+            if rc == -3:
+                return None
+            if rc == 1:
+                raise ValueError(f"project: {self._hist_not_exact(spec)!r} is not device-exact (pow or a libm "
+                                 "function, C or P over a field or several coordinates, or a stack deeper than "
+                                 "the device's); use where='host'")
+            if rc == -2:
+                raise ValueError("project: pft_solver_map refused the programs or the axis (-2)")
+            if rc:
+                raise RuntimeError(f"pft_solver_map failed ({rc}): {self.lib.pft_hip_last_error()}")
+        whole = glob is not None or not several
+        a = (local if glob is None else glob).reshape(-1, cols)
+        d = {k: np.ascontiguousarray(a[k]) for k in MAP_KEYS}
+        d["axis"] = axis
+        d["rows"] = (0, g.total_n3) if whole else (g.first_row, g.n3)
+        return d
+
     # -- f7: snapshots from the resident state -----------------------------------------------------
     def _region(self, sel):
         """the pft_region of a selection (region()) on this simulation's grid; a pft_region is checked"""
@@ -1201,7 +1353,7 @@ class Simulation:
     def run_series(self, final_time=None, saved_files=None, times=None, snapshot_path=None, comment="",
                    diag=True, opts=None, means=False, snapshot_where="host", snapshot_async=False,
                    first_snapshot=0, total_snapshots=None, skip_first=False, regions=None, region_every=1,
-                   snapshot_full=True, formulas=None, variables=None, histograms=None):
+                   snapshot_full=True, formulas=None, variables=None, histograms=None, maps=None, map_every=1):
         """The driver's snapshot loop (intertrack.c:2265-2283).  Snapshot 0 is the state as it
         stands (no solve); snapshot s solves to series_times(t0, final_time, saved_files)[s], or
         to times[s - 1] when times= lists the solve targets.  The steps run device-resident
@@ -1238,7 +1390,35 @@ class Simulation:
         <name>_under, _over, _nan and _selected, so that write_hist_txt(rows, path, key="<name>")
         writes the series.  The specs are compiled once, before the first solve; ValueError up front
         for bad edges, a formula or mask that is not device-exact and for a name whose keys collide
-        with another key of the rows.  All other row keys are unchanged."""
+        with another key of the rows.  All other row keys are unchanged.
+        maps={name: {"formula": ..., "axis": ..., "mask": ...}} (f15; mask optional, see project(); or
+        map_spec()'s result, compiled already): every row of a snapshot whose number is a multiple of
+        map_every also carries <name>, project()'s dict of the whole grid from the device-resident
+        state; with snapshot_path that dict is also written as "<snapshot_path>.<name>.%03d.npz" (by
+        rank 0).  The specs are compiled once, before the first solve; ValueError up front for a bad
+        axis, a formula or mask that is not device-exact and for a name that collides with another
+        key of the rows.  Rows without maps= are unchanged."""
+        map_specs = None
+        if maps is not None:
+            if not isinstance(maps, dict) or not maps:
+                raise ValueError("run_series: maps= is a non-empty {name: spec} dict")
+            map_every = int(map_every)
+            if map_every < 1:
+                raise ValueError(f"map_every must be at least 1, not {map_every}")
+            map_specs = {}
+            for name, sp in maps.items():
+                if not isinstance(sp, dict) or not (sp.get("compiled") or {"formula", "axis"} <= set(sp)):
+                    raise ValueError(f"run_series: map {name!r} needs 'formula' and 'axis'")
+                if not sp.get("compiled"):
+                    extra = set(sp) - {"formula", "axis", "mask"}
+                    if extra:
+                        raise ValueError(f"run_series: map {name!r} has unknown keys {sorted(extra)}")
+                    sp = map_spec(sp["formula"], sp["axis"], sp.get("mask"), variables)
+                bad = self._hist_not_exact(sp)
+                if bad is not None:
+                    raise ValueError(f"run_series: map {name!r}: {bad!r} is not device-exact; evaluate it "
+                                     "with project(where='host') on a downloaded state")
+                map_specs[str(name)] = sp
         hists = None
         if histograms is not None:
             if not isinstance(histograms, dict) or not histograms:
@@ -1280,6 +1460,16 @@ class Simulation:
             if clash:
                 raise ValueError(f"run_series: the histogram keys {clash} collide with other keys of the rows; "
                                  "rename the histogram")
+        if map_specs is not None:
+            taken = self._series_keys()
+            if progs is not None:
+                taken |= {name + "_" + k for name in progs[0] for k in FORMULA_ROW_KEYS}
+            if hists is not None:
+                taken |= {k for name in hists for k in [name] + [name + "_" + s for s in HIST_ROW_KEYS]}
+            clash = sorted(set(map_specs) & taken)
+            if clash:
+                raise ValueError(f"run_series: the map keys {clash} collide with other keys of the rows; "
+                                 "rename the map")
         region_every = int(region_every)
         if region_every < 1:
             raise ValueError(f"region_every must be at least 1, not {region_every}")
@@ -1307,7 +1497,7 @@ class Simulation:
         try:
             rows = self._run_series(targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
                                     snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full,
-                                    progs, hists)
+                                    progs, hists, map_specs, map_every)
         finally:
             if self._snap_pending:
                 self.snapshot_wait()
@@ -1321,7 +1511,7 @@ class Simulation:
 
     def _run_series(self, targets, first, total, end, p_thr, gl_thr, snapshot_path, comment, diag, means,
                     snapshot_where, snapshot_async, skip_first, regions, region_every, snapshot_full, progs=None,
-                    hists=None):
+                    hists=None, map_specs=None, map_every=1):
         not_resident = ("run_series: no state is resident on the device after the solve "
                         "(the host-staged path keeps none)")
 
@@ -1353,6 +1543,12 @@ class Simulation:
                 d = resident(self._histogram, sp)
                 row[name] = d["counts"]
                 row.update({name + "_" + k: d[k] for k in HIST_ROW_KEYS})
+            if s % map_every == 0:
+                for name, sp in (map_specs or {}).items():
+                    d = resident(lambda spec, where, _planes: self._project(spec, where, True), sp)
+                    row[name] = d
+                    if snapshot_path is not None and self.grid.rank == 0:
+                        np.savez("%s.%s.%03d.npz" % (snapshot_path, name, s), **d)
             if snapshot_path is not None and not (s == first and skip_first):
                 info = snapshot_info(self.system.t, self.system.h, end, self.system.delta, self.grid.calc_mode,
                                      snapshot=s, total_snapshots=total, comment=comment)

@@ -2654,6 +2654,10 @@ int pft_slab_destroy(pft_slab* s)
   if (s->hist_host) (void)hipHostFree(s->hist_host);
   for (int i = 0; i < 2; ++i)
     if (s->ev_hist[i]) (void)hipEventDestroy(s->ev_hist[i]);
+  if (s->map_dev) (void)hipFree(s->map_dev);
+  if (s->map_host) (void)hipHostFree(s->map_host);
+  for (int i = 0; i < 2; ++i)
+    if (s->ev_map[i]) (void)hipEventDestroy(s->ev_map[i]);
   if (s->snap_host) {
     // the background writer may still read the image: it finishes first
     (void)pft_snapshot_writer_release(s->snap_host);

@@ -1,10 +1,12 @@
 // pft_reduce.hip -- reductions over the resident state: the ice diagnostics (diag_kernel, f5) and
 // the exact means and z-profiles (means_kernel, f6), the formula diagnostics (formula_kernel, f12)
-// and the histograms of formula values (hist_kernel, f13), with their host API.
+// the histograms of formula values (hist_kernel, f13) and the 2-D maps of formula values (map_kernel,
+// f15), with their host API.
 #include "pft_slab.h"
 
 #include "../../include/pft_formula.h"
 #include "../../include/pft_hist.h"
+#include "../../include/pft_map.h"
 #define PFT_IC_NO_CP   // no loop with a cell's value as its trip count is compiled into formula_kernel
 #include "pft_ic_ops.h"
 
@@ -1357,5 +1359,409 @@ int pft_slab_hist(pft_slab* s, int buf, const pft_ic_prog* value_prog, const pft
 int pft_slab_hist_timing(pft_slab* s, int on) { return slab_timing_set(s, &pft_slab::hist_timing, &pft_slab::ev_hist, on); }
 
 int pft_slab_hist_last_ms(pft_slab* s, double* ms) { return slab_timing_ms(s, &pft_slab::hist_timing, &pft_slab::ev_hist, ms); }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// f15: 2-D maps of formula values (pft_map.h) -- hist_kernel's interpreter and its mask-then-value
+// order, but what is reduced is one record per pixel of the two axes that are kept: the value's
+// counts, extrema and first / last non-zero index along the reduced axis.
+//
+// A pixel's accumulator is MP_WORDS 64-bit words, all zero when neutral: counts add; the minimum
+// and the maximum are the complemented key and the key of diag_key under an integer max; `first`
+// is kept as axis length - index and `last` as index + 1, both under an integer max (0: none).
+// So partial records combine in any order to the same bits, and one hipMemsetAsync resets the map.
+//
+// Axes 0 and 1 (z, y: the reduced axis is strided).  A lane owns the two neighbouring pixels e, e + 1
+// of the kept contiguous extent (axis 0: the whole plane; axis 1: one row of plane o) and marches
+// its share of the reduced axis with both pixels' accumulators in registers (counts and indices in
+// 32 bits: a line has fewer than 2^31 cells), then issues the non-zero words to the pixels' records
+// with 64-bit integer atomics.  The 256 threads are laid out as pw pixel pairs x 256 / pw sub-chunks
+// of the reduced axis (pw a power of two: a 50-cell row takes 32 x 8, not 25 of 256 threads), and
+// map_work_cut cuts the work into items -- (plane or row) x a segment of pw pairs x a chunk of the
+// reduced axis -- so that a small plane still fills the card.  A pair is read with one 16-byte load
+// per field where it is 16-byte aligned at every step of the march (the run starts on a 16-byte
+// boundary and the stride is even) and both pixels exist; else each element alone under its own
+// test.  The two pixels of a pair and the two programs take turns through one copy of the
+// interpreter, as in hist_iter.
+//
+// Axis 2 (x, the contiguous axis): formula_kernel's traversal -- items are segments of one plane,
+// a wave takes 512 consecutive elements per iteration with coalesced 16-byte loads -- and a wave's
+// window spans a few rows.  The wave keeps the partial record of its current row: the counts in
+// scalar registers (ballot and popcount over the lanes of that row), the keys and first / last per
+// lane; for each row a load's 128 elements touch (a wave-uniform loop, as diag_iter's over planes)
+// the lanes of that row add theirs, and when the row changes the per-lane words are reduced by a
+// shuffle maximum and lane 0 adds the row's non-zero words to the pixel's record.  While the row
+// does not change nothing leaves the registers.
+//
+// LDS: the 30 720 bytes of the stack column.  No floating-point atomic, no compare-and-swap.
+enum { MP_SELECTED = 0, MP_NONZERO, MP_NONFINITE, MP_MIN, MP_MAX, MP_FIRST, MP_LAST, MP_WORDS };
+#define PFT_MAP_MIN_STEPS 16   // a thread's share of the reduced axis is not cut below this (axes 0, 1)
+static_assert(sizeof(pft_map_px) == 8 * MP_WORDS, "pft_map_px is seven 64-bit words, no padding");
+
+struct MapAcc {
+  unsigned sel, nz, nf, first, last;   // (first: axis length - index, last: index + 1; 0: none)
+  unsigned long long kmin, kmax;       // (0: no value yet)
+};
+
+__device__ __forceinline__ void map_acc_zero(MapAcc& a)
+{
+  a.sel = a.nz = a.nf = a.first = a.last = 0;
+  a.kmin = a.kmax = 0;
+}
+
+// one cell into a lane's accumulator: sel -- the cell exists and is selected, x its value, `at` its
+// index along the reduced axis of `len` cells
+__device__ __forceinline__ void map_acc_take(MapAcc& a, bool sel, double x, unsigned at, unsigned len)
+{
+  const bool nz = sel && x != 0;   // (a NaN is "true")
+  a.sel += sel ? 1u : 0u;
+  a.nz += nz ? 1u : 0u;
+  a.nf += sel && !diag_finite(x) ? 1u : 0u;
+  const unsigned f = nz ? len - at : 0u, l = nz ? at + 1u : 0u;
+  a.first = f > a.first ? f : a.first;
+  a.last = l > a.last ? l : a.last;
+  if (sel && x == x) {
+    const unsigned long long key = diag_key(x);
+    a.kmax = key > a.kmax ? key : a.kmax;
+    a.kmin = ~key > a.kmin ? ~key : a.kmin;
+  }
+}
+
+// the non-zero words of an accumulator to a pixel's record
+__device__ __forceinline__ void map_acc_issue(const MapAcc& a, unsigned long long* __restrict__ dst)
+{
+  if (a.sel) atomicAdd(&dst[MP_SELECTED], (unsigned long long)a.sel);
+  if (a.nz) atomicAdd(&dst[MP_NONZERO], (unsigned long long)a.nz);
+  if (a.nf) atomicAdd(&dst[MP_NONFINITE], (unsigned long long)a.nf);
+  if (a.kmin) atomicMax(&dst[MP_MIN], a.kmin);
+  if (a.kmax) atomicMax(&dst[MP_MAX], a.kmax);
+  if (a.first) atomicMax(&dst[MP_FIRST], (unsigned long long)a.first);
+  if (a.last) atomicMax(&dst[MP_LAST], (unsigned long long)a.last);
+}
+
+// a cell's mask (entries m0..m1; m0 == m1: none) and then its value (c0..c1) on the lane's stack
+// column; sel: in, the cell exists; out, it is also selected
+__device__ __forceinline__ double map_cell(const FormulaProgs& P, int c0, int c1, int m0, int m1, double u, double p,
+                                           double g, int i, int j, int k, double* stack, bool& sel)
+{
+  double x = 0.0;
+#pragma unroll 1
+  for (int pass = m1 > m0 ? 0 : 1; pass < 2; ++pass) {
+    const double val = formula_eval(P, pass ? c0 : m0, pass ? c1 : m1, u, p, g, i, j, k, stack);
+    if (pass == 0)
+      sel = sel && val != 0;   // (a NaN is "true")
+    else
+      x = val;
+  }
+  return x;
+}
+
+// the cut of axes 0 and 1 (map_work_cut): 2^pw_log2 pixel pairs per workgroup, segs segments of them
+// per kept extent, chunks chunks of chunk_len cells of the reduced axis
+struct MapCut {
+  int pw_log2, segs, chunks, chunk_len;
+};
+
+// axis 2's wave state: the partial record of row `row` of the item's plane (-1: none yet)
+struct MapRow {
+  int row;
+  unsigned sel, nz, nf;                // wave-uniform counts
+  unsigned first, last;                // per lane
+  unsigned long long kmin, kmax;       // per lane
+};
+
+__device__ __forceinline__ void map_row_flush(MapRow& w, int lane, unsigned long long* __restrict__ dst)
+{
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    unsigned long long o;
+    unsigned q;
+    o = __shfl_xor(w.kmin, off, 64), w.kmin = o > w.kmin ? o : w.kmin;
+    o = __shfl_xor(w.kmax, off, 64), w.kmax = o > w.kmax ? o : w.kmax;
+    q = __shfl_xor(w.first, off, 64), w.first = q > w.first ? q : w.first;
+    q = __shfl_xor(w.last, off, 64), w.last = q > w.last ? q : w.last;
+  }
+  if (lane == 0) {
+    MapAcc a;
+    a.sel = w.sel, a.nz = w.nz, a.nf = w.nf, a.first = w.first, a.last = w.last, a.kmin = w.kmin, a.kmax = w.kmax;
+    map_acc_issue(a, dst);
+  }
+  w.sel = w.nz = w.nf = w.first = w.last = 0;
+  w.kmin = w.kmax = 0;
+}
+
+// the lanes of row w.row add their cell (in: it exists, is selected and lies in that row)
+__device__ __forceinline__ void map_row_take(MapRow& w, bool in, double x, int i, int n1)
+{
+  const bool nz = in && x != 0;
+  w.sel += (unsigned)__popcll(__ballot(in));
+  w.nz += (unsigned)__popcll(__ballot(nz));
+  w.nf += (unsigned)__popcll(__ballot(in && !diag_finite(x)));
+  const unsigned f = nz ? (unsigned)(n1 - i) : 0u, l = nz ? (unsigned)(i + 1) : 0u;
+  w.first = f > w.first ? f : w.first;
+  w.last = l > w.last ? l : w.last;
+  if (in && x == x) {
+    const unsigned long long key = diag_key(x);
+    w.kmax = key > w.kmax ? key : w.kmax;
+    w.kmin = ~key > w.kmin ? ~key : w.kmin;
+  }
+}
+
+// acc: MP_WORDS words per pixel, row-major [n2][n1] (AXIS 0), [n3][n1] (1), [n3][n2] (2).
+// AXIS 2: segs / seg_len are plane_work_cut's and cut is not used
+template <int AXIS>
+__global__ __launch_bounds__(PFT_DBLOCK) void map_kernel(const double* __restrict__ fu, const double* __restrict__ fp,
+                                                         const double* __restrict__ fg, int plane, int head, int n1,
+                                                         int n2, int n3, MapCut cut, int segs, int seg_len,
+                                                         FormulaProgs P, int has_mask,
+                                                         unsigned long long* __restrict__ acc)
+{
+  __shared__ double s_stack[PFT_FORMULA_SLOTS * PFT_DBLOCK];
+  const int c0 = P.meta[0], c1 = P.meta[1];
+  const int m0 = has_mask ? P.meta[3] : 0, m1 = has_mask ? P.meta[4] : 0;
+  const int need = P.meta[2] | (has_mask ? P.meta[5] : 0);
+  double* stack = s_stack + threadIdx.x;
+  if (AXIS < 2) {
+    const int ext = AXIS == 0 ? plane : n1;      // the kept contiguous extent
+    const int len = AXIS == 0 ? n3 : n2;         // the reduced axis
+    const long stride = AXIS == 0 ? plane : n1;
+    const long outer = AXIS == 0 ? 1 : n3;
+    const int pw = 1 << cut.pw_log2, sc = PFT_DBLOCK >> cut.pw_log2;
+    const int tp = (int)threadIdx.x & (pw - 1), sub = (int)threadIdx.x >> cut.pw_log2;
+    const int sub_len = (cut.chunk_len + sc - 1) / sc;
+    const bool aligned = head == 0 && (stride & 1) == 0;
+    const long items = outer * cut.segs * cut.chunks;
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {
+      const int c = (int)(item % cut.chunks);
+      const long t = item / cut.chunks;
+      const int sg = (int)(t % cut.segs), o = (int)(t / cut.segs);
+      const int e = 2 * (sg * pw + tp);
+      const bool v0 = e < ext, v1 = e + 1 < ext;
+      const int c_end = (c + 1) * cut.chunk_len < len ? (c + 1) * cut.chunk_len : len;
+      const int r_begin = c * cut.chunk_len + sub * sub_len;
+      int r_end = r_begin + sub_len < c_end ? r_begin + sub_len : c_end;
+      if (!v0) r_end = r_begin;   // (no pixel: no step)
+      // the two pixels' table indices along the kept axes
+      int i0 = 0, j0 = 0, i1 = 0, j1 = 0;
+      if (AXIS == 0) {
+        if (need & FM_NEED_IJ) {
+          const int e0 = v0 ? e : 0, e1 = v1 ? e + 1 : 0;
+          j0 = e0 / n1, i0 = e0 - j0 * n1;
+          j1 = e1 / n1, i1 = e1 - j1 * n1;
+        }
+      } else {
+        i0 = v0 ? e : 0, i1 = v1 ? e + 1 : 0;
+      }
+      MapAcc a0, a1;
+      map_acc_zero(a0);
+      map_acc_zero(a1);
+      long at = (long)o * plane + (long)r_begin * stride + e;
+      for (int r = r_begin; r < r_end; ++r, at += stride) {
+        double u[2] = {0.0, 0.0}, p[2] = {0.0, 0.0}, g[2] = {0.0, 0.0};
+        if (aligned && v1) {
+          if (need & FM_NEED_U) {
+            const double2 q = *reinterpret_cast<const double2*>(fu + at);
+            u[0] = q.x, u[1] = q.y;
+          }
+          if (need & FM_NEED_P) {
+            const double2 q = *reinterpret_cast<const double2*>(fp + at);
+            p[0] = q.x, p[1] = q.y;
+          }
+          if (need & FM_NEED_GL) {
+            const double2 q = *reinterpret_cast<const double2*>(fg + at);
+            g[0] = q.x, g[1] = q.y;
+          }
+        } else {
+          if (need & FM_NEED_U) u[0] = fu[at];
+          if (need & FM_NEED_P) p[0] = fp[at];
+          if (need & FM_NEED_GL) g[0] = fg[at];
+          if (v1 && (need & FM_NEED_U)) u[1] = fu[at + 1];
+          if (v1 && (need & FM_NEED_P)) p[1] = fp[at + 1];
+          if (v1 && (need & FM_NEED_GL)) g[1] = fg[at + 1];
+        }
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+          bool sel = h ? v1 : true;
+          const int ti = h ? i1 : i0, tj = AXIS == 0 ? (h ? j1 : j0) : r, tk = AXIS == 0 ? r : o;
+          const double x = map_cell(P, c0, c1, m0, m1, h ? u[1] : u[0], h ? p[1] : p[0], h ? g[1] : g[0], ti, tj, tk,
+                                    stack, sel);
+          if (h == 0)
+            map_acc_take(a0, sel, x, (unsigned)r, (unsigned)len);
+          else
+            map_acc_take(a1, sel, x, (unsigned)r, (unsigned)len);
+        }
+      }
+      if (v0) {
+        unsigned long long* dst = acc + ((size_t)o * n1 + (size_t)e) * MP_WORDS;   // (AXIS 0: o = 0)
+        map_acc_issue(a0, dst);
+        map_acc_issue(a1, dst + MP_WORDS);   // (all zero without a second pixel: nothing is issued)
+      }
+    }
+  } else {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    MapRow w;
+    w.row = -1;
+    w.sel = w.nz = w.nf = w.first = w.last = 0;
+    w.kmin = w.kmax = 0;
+    const long items = (long)n3 * segs;
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {
+      const ItemFrame it = item_frame(item, segs, seg_len, plane, head);
+      const int k = it.k, first = it.first, r_lo = it.r_lo, r_hi = it.r_hi, span = it.span;
+      const double* wu = fu + it.e_base;   // (e_base = -1: one before the run, never read at r = 0)
+      const double* wp = fp + it.e_base;
+      const double* wg = fg + it.e_base;
+      unsigned long long* rows = acc + (size_t)k * n2 * MP_WORDS;
+      for (int r0 = PFT_DIAG_WAVE_ELEMS * wave; r0 < span; r0 += PFT_DIAG_WAVE_ELEMS * (PFT_DBLOCK / 64)) {
+        const bool full = r0 >= r_lo && r0 + PFT_DIAG_WAVE_ELEMS <= r_hi;
+#pragma unroll 1
+        for (int jj = 0; jj < PFT_DIAG_UNROLL; ++jj) {
+          const int rb = r0 + 128 * jj, r = rb + 2 * lane;
+          // the load's existing elements [wa, wb] (wave-uniform)
+          const int wa = rb > r_lo ? rb : r_lo, wb = (rb + 128 < r_hi ? rb + 128 : r_hi) - 1;
+          if (wb < wa) continue;
+          double u[2] = {0.0, 0.0}, p[2] = {0.0, 0.0}, g[2] = {0.0, 0.0};
+          bool v[2];
+          formula_load(full, need, wu, wp, wg, r, r_lo, r_hi, u, p, g, v);
+          double x0 = 0.0, x1 = 0.0;
+          bool s0 = false, s1 = false;
+          int i0 = 0, j0 = 0, i1 = 0, j1 = 0;
+#pragma unroll 1
+          for (int h = 0; h < 2; ++h) {
+            const bool vh = h ? v[1] : v[0];
+            // the node's place in its plane; a slot outside the item evaluates node 0 (inside every
+            // table) and is left out of every count below
+            const int e = vh ? first + (r + h - r_lo) : 0;
+            const int j = e / n1, i = e - j * n1;
+            bool sel = vh;
+            const double x = map_cell(P, c0, c1, m0, m1, h ? u[1] : u[0], h ? p[1] : p[0], h ? g[1] : g[0], i, j, k,
+                                      stack, sel);
+            if (h == 0)
+              x0 = x, s0 = sel, i0 = i, j0 = j;
+            else
+              x1 = x, s1 = sel, i1 = i, j1 = j;
+          }
+          const int ja = (first + (wa - r_lo)) / n1, jb = (first + (wb - r_lo)) / n1;
+          for (int jr = ja; jr <= jb; ++jr) {
+            if (jr != w.row) {
+              if (w.row >= 0) map_row_flush(w, lane, rows + (size_t)w.row * MP_WORDS);
+              w.row = jr;
+            }
+            map_row_take(w, s0 && j0 == jr, x0, i0, n1);
+            map_row_take(w, s1 && j1 == jr, x1, i1, n1);
+          }
+        }
+      }
+      // (the next item is another plane or another wave's rows: nothing is kept across items)
+      if (w.row >= 0) map_row_flush(w, lane, rows + (size_t)w.row * MP_WORDS);
+      w.row = -1;
+    }
+  }
+}
+
+// The cut of axes 0 and 1 into work items, beside plane_work_cut and against the same cap of 8
+// workgroups per CU: the workgroup's threads are 2^pw_log2 pixel pairs (the first power of two that
+// covers the kept extent's pairs, 256 at most) x the sub-chunks that are left; the reduced axis is
+// cut into as many chunks as the cap allows, but a thread's share stays PFT_MAP_MIN_STEPS cells or
+// more: every chunk ends with up to 7 atomics per pixel.  An item is chunk c of segment g of the
+// kept extent o (axis 0: the plane, o = 0; axis 1: the row of plane o), item = (o * segs + g) *
+// chunks + c.
+static void map_work_cut(const pft_slab* s, int axis, MapCut* cut, unsigned* wgs)
+{
+  const long ext = axis == 0 ? s->plane : s->d.n1, len = axis == 0 ? s->d.n3 : s->d.n2, outer = axis == 0 ? 1 : s->d.n3;
+  const long cap = s->diag_wgs > 0 ? s->diag_wgs : 8L * (s->n_cu > 0 ? s->n_cu : 256);
+  const long pairs = (ext + 1) / 2;
+  int lg = 0;
+  while (lg < 8 && (1L << lg) < pairs) ++lg;
+  const long pw = 1L << lg, sc = PFT_DBLOCK / pw;
+  const long segs = (pairs + pw - 1) / pw;
+  long want = cap / (segs * outer);
+  if (want < 1) want = 1;
+  long chunk_len = (len + want - 1) / want;
+  if (chunk_len < PFT_MAP_MIN_STEPS * sc) chunk_len = PFT_MAP_MIN_STEPS * sc;
+  if (chunk_len > len) chunk_len = len;
+  const long chunks = (len + chunk_len - 1) / chunk_len;
+  const long items = outer * segs * chunks;
+  cut->pw_log2 = lg, cut->segs = (int)segs, cut->chunks = (int)chunks, cut->chunk_len = (int)chunk_len;
+  *wgs = (unsigned)(items < cap ? items : cap);
+}
+
+extern "C" {
+
+int pft_slab_map(pft_slab* s, int buf, const pft_ic_prog* value_prog, const pft_ic_prog* mask_prog, int axis,
+                 pft_map_px* out_local)
+{
+  if (!s || !value_prog || !out_local || buf < 0 || buf >= PFT_BUF_COUNT || axis < 0 || axis > 2) return -2;
+  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_map");
+  const long plane = s->plane, n = (long)s->d.n3 * plane;
+  const int n1 = s->d.n1, n2 = s->d.n2, n3 = s->d.n3;
+  if (n > 0x7fffffffL || plane > PFT_MEANS_MAX_PLANE) return -2;
+  const pft_ic_prog* list[2] = {value_prog, mask_prog};
+  const int nprog = mask_prog ? 2 : 1;
+  long entries = 0, tvals = 0;
+  int rc_pack = formula_progs_check(s, nprog, list, &entries, &tvals);
+  if (rc_pack) return rc_pack;
+  FormulaProgs P;
+  size_t blob = 0;
+  if ((rc_pack = formula_progs_pack(s, nprog, list, entries, tvals, 0, nullptr, &P, nullptr, &blob))) return rc_pack;
+  const size_t pixels = (size_t)(axis == 0 ? n2 : n3) * (size_t)(axis == 2 ? n2 : n1);
+  const long axis_len = axis == 0 ? n3 : (axis == 1 ? n2 : n1);
+  const size_t bytes = sizeof(unsigned long long) * MP_WORDS * pixels;
+  if (bytes > s->map_cap) {
+    if (s->map_dev) HIPCHK(hipFree(s->map_dev));
+    if (s->map_host) HIPCHK(hipHostFree(s->map_host));
+    s->map_dev = s->map_host = nullptr;
+    s->map_cap = 0;
+    HIPCHK(hipMalloc((void**)&s->map_dev, bytes));
+    HIPCHK(hipHostMalloc((void**)&s->map_host, bytes, hipHostMallocDefault));
+    s->map_cap = bytes;
+  }
+  int head, segs = 0, seg_len = 0;
+  unsigned wgs;
+  MapCut cut = {0, 0, 0, 0};
+  const double* fu = slab_fields(s, buf, &head);
+  if (axis == 2)
+    plane_work_cut(s, &segs, &seg_len, &wgs);
+  else
+    map_work_cut(s, axis, &cut, &wgs);
+  HIPCHK(hipMemcpyAsync(s->formula_prog_dev, s->formula_prog_host, blob, hipMemcpyHostToDevice, s->stream));
+  // no state carries over between calls: every accumulator word is zeroed on the stream first
+  HIPCHK(hipMemsetAsync(s->map_dev, 0, bytes, s->stream));
+  if (s->map_timing) HIPCHK(hipEventRecord(s->ev_map[0], s->stream));
+  const double *fp = fu + s->fs, *fg = fu + 2 * s->fs;
+  const int has_mask = mask_prog ? 1 : 0;
+  if (axis == 0)
+    map_kernel<0><<<wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fp, fg, (int)plane, head, n1, n2, n3, cut, segs, seg_len, P, has_mask,
+                                                     s->map_dev);
+  else if (axis == 1)
+    map_kernel<1><<<wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fp, fg, (int)plane, head, n1, n2, n3, cut, segs, seg_len, P, has_mask,
+                                                     s->map_dev);
+  else
+    map_kernel<2><<<wgs, PFT_DBLOCK, 0, s->stream>>>(fu, fp, fg, (int)plane, head, n1, n2, n3, cut, segs, seg_len, P, has_mask,
+                                                     s->map_dev);
+  HIPCHK(hipGetLastError());
+  if (s->map_timing) HIPCHK(hipEventRecord(s->ev_map[1], s->stream));
+  HIPCHK(hipMemcpyAsync(s->map_host, s->map_dev, bytes, hipMemcpyDeviceToHost, s->stream));
+  const int rc = slab_wait(s, nullptr, "pft_slab_map");
+  if (rc) return rc;
+  const double inf = __builtin_inf();
+  for (size_t q = 0; q < pixels; ++q) {
+    const unsigned long long* h = s->map_host + q * MP_WORDS;
+    pft_map_px* o = &out_local[q];
+    o->selected = (long long)h[MP_SELECTED];
+    o->nonzero = (long long)h[MP_NONZERO];
+    o->nonfinite = (long long)h[MP_NONFINITE];
+    o->min = h[MP_MIN] ? diag_unkey(~h[MP_MIN]) : inf;
+    o->max = h[MP_MAX] ? diag_unkey(h[MP_MAX]) : -inf;
+    o->first = h[MP_FIRST] ? axis_len - (long long)h[MP_FIRST] : -1;
+    o->last = h[MP_LAST] ? (long long)h[MP_LAST] - 1 : -1;
+  }
+  return 0;
+}
+
+int pft_slab_map_timing(pft_slab* s, int on) { return slab_timing_set(s, &pft_slab::map_timing, &pft_slab::ev_map, on); }
+
+int pft_slab_map_last_ms(pft_slab* s, double* ms) { return slab_timing_ms(s, &pft_slab::map_timing, &pft_slab::ev_map, ms); }
 
 }  // extern "C"

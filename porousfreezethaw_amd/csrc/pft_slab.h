@@ -220,6 +220,13 @@ struct pft_slab {
   size_t hist_cap;
   int hist_timing;
   hipEvent_t ev_hist[2];
+  // f15 maps (pft_slab_map): 7 accumulator words per pixel and their pinned host copy, grown on
+  // demand (map_cap bytes each); the programs travel in the f12 blob; events around the kernel
+  unsigned long long* map_dev;
+  unsigned long long* map_host;      // pinned
+  size_t map_cap;
+  int map_timing;
+  hipEvent_t ev_map[2];
   // f7 snapshots (pft_slab_snapshot_export / pft_slab_image): the image-sized pinned, host-mapped
   // buffer the background writer reads (allocated by the first call, freed at destroy once the
   // writer is done with it), the device staging image of the staged host link, events around the

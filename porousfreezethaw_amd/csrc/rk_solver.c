@@ -22,6 +22,7 @@
 #include "../../include/pft_frontend.h"
 #include "../../include/pft_formula.h"
 #include "../../include/pft_hist.h"
+#include "../../include/pft_map.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -926,6 +927,128 @@ int pft_solver_hist(int nv, const int * vops, const double * vargs, int nm, cons
 	if(local) *local = mine.h;
 	if(local_counts) memcpy(local_counts, mine.counts, sizeof(long long) * (size_t)nbins);
 	drop_records(all, &mine);
+	return 0;
+}
+
+int pft_solver_map(int nv, const int * vops, const double * vargs, int nm, const int * mops, const double * margs,
+                   int axis, pft_map_px * global, pft_map_px * local)
+{
+	/* f15: the map of the device-resident x, under pft_solver_hist's rules.  Every rank compiles both
+	   programs first; the outcome, a 64-bit hash of the axis, of whether a global map is wanted and
+	   of both programs, and the slab's rows travel in one allgather, so that ranks that were given
+	   different maps all answer -2 before any device work.  Then each rank reduces its slab.  With
+	   `global` its share travels with its status (gather_records): for axis 0 its partial map, merged
+	   in rank order; for axes 1 and 2 its rows, every rank sending as many as the tallest slab has
+	   (the rest neutral), put at the slab's first row.  Without `global` only the status travels. */
+	struct map_first { long long code; unsigned long long hash; long long n3, first_row; };
+	char * all, * msg = NULL;
+	long long status_only = 0;
+	struct map_first first, firsts[PFT_DIAG_MAX_RANKS];
+	pft_ic_prog pv, pm;
+	pft_grid g;
+	pft_comm * c = comm();
+	const int nprocs = pft_comm_size(c);
+	const int masked = mops || margs || nm;
+	const int want_global = global != NULL;
+	int rc, r, rows = 0, cols = 0;
+	long q, n = 0, send = 0, max_n3 = 0;
+	size_t used = sizeof status_only;
+	if(!local) return -2;
+	if((rc = resident_state(1))) return rc;
+	if(nprocs > PFT_DIAG_MAX_RANKS) return -2;
+	memset(&pv, 0, sizeof pv);
+	memset(&pm, 0, sizeof pm);
+	memset(&first, 0, sizeof first);
+	first.hash = 0xcbf29ce484222325ULL;
+	if(nv < 1 || nv > PFT_FORMULA_MAX_ENTRIES || !vops || !vargs || axis < 0 || axis > 2
+	   || (masked && (nm < 1 || !mops || !margs || nv + nm > PFT_FORMULA_MAX_ENTRIES)) || pft_model_get_grid(&g)
+	   || pft_map_dims(&g, axis, &rows, &cols)) rc = -2;
+	if(!rc) {
+		first.hash = hist_hash(first.hash, &axis, sizeof axis);
+		first.hash = hist_hash(first.hash, &want_global, sizeof want_global);
+		first.hash = hist_hash(first.hash, &nv, sizeof nv);
+		first.hash = hist_hash(first.hash, vops, sizeof(int) * (size_t)nv);
+		first.hash = hist_hash(first.hash, vargs, sizeof(double) * (size_t)nv);
+		first.hash = hist_hash(first.hash, &nm, sizeof nm);
+		if(masked) {
+			first.hash = hist_hash(first.hash, mops, sizeof(int) * (size_t)nm);
+			first.hash = hist_hash(first.hash, margs, sizeof(double) * (size_t)nm);
+		}
+		first.n3 = g.n3;
+		first.first_row = g.first_row;
+		rc = pft_formula_compile(&g, nv, vops, vargs, &pv);
+		if(!rc && masked) rc = pft_formula_compile(&g, nm, mops, margs, &pm);
+	}
+	if(nprocs > 1) {
+		int crc;
+		long long v = 0;
+		first.code = compile_rank(rc);
+		crc = pft_comm_allgather(c, &first, (int)sizeof first, firsts);
+		if(crc) {
+			pft_ic_prog_free(&pv);
+			pft_ic_prog_free(&pm);
+			R.last_status = crc;
+			return PFT_SOLVE_DEVICE_ERROR;
+		}
+		for(r = 0; r < nprocs; r++) if(firsts[r].code > v) v = firsts[r].code;
+		/* (ranks that all compiled: the same map on every one of them, or -2) */
+		for(r = 1; r < nprocs && !v; r++) if(firsts[r].hash != firsts[0].hash) v = 2;
+		rc = compile_code(v);
+	}
+	if(rc) {
+		pft_ic_prog_free(&pv);
+		pft_ic_prog_free(&pm);
+		return rc;
+	}
+	n = (long)rows * cols;
+	if(nprocs > 1 && want_global) {
+		/* what every rank sends: its partial map (axis 0), or as many rows as the tallest slab has */
+		long long bad;
+		for(r = 0; r < nprocs; r++) if(firsts[r].n3 > max_n3) max_n3 = (long)firsts[r].n3;
+		send = axis == 0 ? n : max_n3 * cols;
+		used = sizeof status_only + sizeof(pft_map_px) * (size_t)send;
+		msg = (char *)malloc(used);
+		bad = !msg;
+		if((rc = pft_comm_allreduce_max_i64(c, &bad)) || bad) {
+			free(msg);
+			pft_ic_prog_free(&pv);
+			pft_ic_prog_free(&pm);
+			if(rc) R.last_status = rc;
+			return rc ? PFT_SOLVE_DEVICE_ERROR : -1;
+		}
+	}
+	rc = pft_slab_map(R.slab, PFT_BUF_X, &pv, masked ? &pm : NULL, axis, local);
+	pft_ic_prog_free(&pv);
+	pft_ic_prog_free(&pm);
+	if(!rc && axis == 0 && g.first_row) {
+		/* the slab counts its own planes from 0 */
+		for(q = 0; q < n; q++) {
+			if(local[q].first >= 0) local[q].first += g.first_row;
+			if(local[q].last >= 0) local[q].last += g.first_row;
+		}
+	}
+	if(msg) {
+		pft_map_px * rec = (pft_map_px *)(msg + sizeof status_only);
+		if(!rc) memcpy(rec, local, sizeof(pft_map_px) * (size_t)n);
+		for(q = rc ? 0 : n; q < send; q++) pft_map_init(&rec[q]);
+	}
+	rc = gather_records(rc, msg ? (void *)msg : (void *)&status_only, used, &all);
+	if(rc) {
+		free(msg);
+		return rc;
+	}
+	if(global && nprocs == 1) memcpy(global, local, sizeof(pft_map_px) * (size_t)n);
+	else if(global) {
+		const long total = axis == 0 ? n : (long)g.total_n3 * cols;
+		for(q = 0; q < total; q++) pft_map_init(&global[q]);
+		for(r = 0; r < nprocs; r++) {
+			const pft_map_px * rec = (const pft_map_px *)(all + (size_t)r*used + sizeof status_only);
+			if(axis == 0) pft_map_combine(n, global, rec);
+			else memcpy(global + firsts[r].first_row * cols, rec, sizeof(pft_map_px) * (size_t)(firsts[r].n3 * cols));
+		}
+	}
+	drop_records(all, msg ? (void *)msg : (void *)&status_only);
+	free(msg);
 	return 0;
 }
 

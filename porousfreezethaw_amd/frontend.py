@@ -521,7 +521,7 @@ class Case:
 
     def run(self, nprocs=1, rank=0, beads=None, snapshot_path=None, comment="", diag=True, opts=None,
             means=False, snapshot_where="host", snapshot_async=False, regions=None, region_every=1,
-            snapshot_full=True, formulas=None, histograms=None, **kw):
+            snapshot_full=True, formulas=None, histograms=None, maps=None, map_every=1, **kw):
         """the whole case as the driver runs it (intertrack.c:2265-2283): this slab's simulation
         (simulation(); **kw goes to it), then saved_files snapshots up to final_time
         (Simulation.run_series; means=True: every row also carries the exact means).  Returns the
@@ -539,7 +539,8 @@ class Case:
         own evaluator, so every variable of the parameter file (u_star, L3, water_cp, ...) can appear;
         given here in Python -- the reference driver has no Params word for them either.
         histograms={name: {"formula", "bins", "range", "mask"}} (f13): run_series' histograms, their
-        formulas and masks compiled with this case's own evaluator in the same way."""
+        formulas and masks compiled with this case's own evaluator in the same way.
+        maps={name: {"formula", "axis", "mask"}} (f15), map_every: run_series' maps, compiled likewise."""
         final_time, saved_files, first, skip_first = self.final_time, self.saved_files, 0, False
         if formulas is not None:
             from . import formula_programs
@@ -554,6 +555,16 @@ class Case:
                     raise ValueError(f"histogram {name!r} needs 'formula' and 'bins'")
                 compiled[name] = hist_spec(sp["formula"], sp["bins"], sp.get("range"), sp.get("mask"), self.ev)
             histograms = compiled
+        if maps is not None:
+            from . import map_spec
+            if not isinstance(maps, dict) or not maps:
+                raise ValueError("maps= is a non-empty {name: spec} dict")
+            compiled = {}
+            for name, sp in maps.items():
+                if not isinstance(sp, dict) or not {"formula", "axis"} <= set(sp):
+                    raise ValueError(f"map {name!r} needs 'formula' and 'axis'")
+                compiled[name] = map_spec(sp["formula"], sp["axis"], sp.get("mask"), self.ev)
+            maps = compiled
         if self.continue_series and not self.icond_mode:
             warnings.warn("continue_series is only meaningful when the initial conditions are loaded from file")
         elif self.continue_series:
@@ -566,7 +577,7 @@ class Case:
                                   diag=diag, opts=opts, means=means, snapshot_where=snapshot_where,
                                   snapshot_async=snapshot_async, first_snapshot=first, skip_first=skip_first,
                                   regions=regions, region_every=region_every, snapshot_full=snapshot_full,
-                                  formulas=formulas, histograms=histograms)
+                                  formulas=formulas, histograms=histograms, maps=maps, map_every=map_every)
         finally:
             sim.close()
 
