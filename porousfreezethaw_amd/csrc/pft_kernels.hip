@@ -309,17 +309,15 @@ struct StageArgs {
   // from them with the solver's own expressions (gate_scalars).
   const unsigned long long* gate;
   unsigned long long gseq;
-  // ... and the decision: the speculative stage 1's extra workgroup, once it has the error norm,
-  // decides the step as hybrid2.c:578-611 does and writes it to gdev (for the launches gated on
-  // it) and to pinned gpin (for the host, which takes its own decision and compares bit for bit).
-  // gdec_seq: its sequence number; dt, dh: t and h of the step being decided (a gated launch
-  // takes them from its gate); the solve's constants: final time, delta, h_min, delta_mode ==
-  // DELTA_LOCAL, handle_nan.
+  // ... and the decision: the speculative stage 1's extra workgroup, once it has the error norm, decides
+  // the step with the solver's own controller (pft_stepctl.h) and writes it to gdev (for the launches gated
+  // on it) and to pinned gpin (for the host, which takes its own decision and compares bit for bit).  gdec_seq:
+  // its number; dt, dh: t and h of the step decided (a gated launch's: from its gate); k: the solve's constants.
   unsigned long long* gdev;
   unsigned long long* gpin;
   unsigned long long gdec_seq;
-  double dt, dh, d_final, d_delta, d_hmin;
-  int d_local, d_nan;
+  double dt, dh;
+  pft_stepctl_consts k;
   int d_flip;          // test hook (env PFT_GATE_FLIP = N): every N-th accepted decision leaves the
                        // device with the last bit of its h flipped, so the host's check must discard
                        // and relaunch that step (tests/test_gate_gpu.py)
@@ -327,94 +325,36 @@ struct StageArgs {
 
 #define PFT_GATE_SKIP (1ULL << 63)
 
-// the scalars of a gated launch from the decided (t, h), exactly as rk_solver.c's run_fused and
-// run_stage form them (hybrid2.c:355: h/2.0, h/3.0, h/6.0, h/8.0; the stage times t + h3, t + h2,
-// t + h; equation.c:110 T_top; the stage-input coefficients h/3.0, h/6.0, h/8.0, h).  IEEE
-// division and addition are correctly rounded on both sides (-ffp-contract=off): the same bits.
+// a gated launch's scalars from the decided (t, h) by the function the host calls (pft_stepctl_stage; a
+// gated stage 1 is the speculative one, 6) and equation.c:110 T_top: correctly rounded, the same bits
 template <int STAGE>
 __device__ __forceinline__ void gate_scalars(StageArgs& a, const pft_consts& c, double t, double h)
 {
-  const double h2 = h / 2.0, h3 = h / 3.0, h6 = h / 6.0, h8 = h / 8.0;
-  double ts = t + h;
-  if (STAGE == 1) {                      // the speculative stage 1 of the next step (coef 0, h 0)
-    a.coef = 0.0;
-    a.h = h;
-    a.cin = h;
-  } else {
-    ts = STAGE <= 3 ? t + h3 : (STAGE == 4 ? t + h2 : t + h);
-    a.coef = STAGE == 2 ? h6 : (STAGE == 3 ? h8 : (STAGE == 4 ? h : h3));
-    a.h = h;
-    a.cin = STAGE == 2 ? h / 3.0 : (STAGE == 3 ? h / 6.0 : (STAGE == 4 ? h / 8.0 : h));
-  }
-  a.T_top = ts < c.phase_switch_time ? c.top_temp1 : c.top_temp2;
+  const pft_stage_scalars s = pft_stepctl_stage(STAGE == 1 ? 6 : STAGE, t, h);
+  a.coef = s.coef;
+  a.h = h;
+  a.cin = s.cin;
+  a.T_top = s.ts < c.phase_switch_time ? c.top_temp1 : c.top_temp2;
   if (STAGE == 5) a.gl_keep = a.gl_keep && isfinite(a.coef);
 }
 
-// x^0.2 rounded to nearest, for the step-size control.  glibc's pow (the host's) rounds correctly
-// but for rare hard cases; ocml's is within ~1 ulp (10% of the decisions differed in the last
-// bit).  So the candidate c = pow(x, 0.2) is checked against the midpoints to its neighbours in
-// double-double arithmetic: v = x^0.2 > m  <=>  x > m^(1/0.2), and 1/0.2 = 5 / (1 + 5 e) with
-// 0.2 = 1/5 + e, e = 2^-54 / 5, so m^(1/0.2) = m^5 (1 - 25 e ln m) to far below the ~2^-53 the
-// comparison needs.  Outside a safe range the candidate stays (the host's check catches it).
-struct pft_dd {
-  double hi, lo;
-};
-__host__ __device__ __forceinline__ pft_dd dd_norm(double a, double b)
-{
-  const double s = a + b;
-  return {s, b - (s - a)};
-}
-__host__ __device__ __forceinline__ pft_dd dd_mul(pft_dd a, pft_dd b)
-{
-  const double p = a.hi * b.hi;
-  double e = fma(a.hi, b.hi, -p);
-  e += a.hi * b.lo + a.lo * b.hi;
-  return dd_norm(p, e);
-}
-// sign of x - m^(1/0.2) for the midpoint m = c + d (d = half the gap to a neighbour of c)
-__host__ __device__ __forceinline__ int pow02_side(double x, double c, double d, double k)
-{
-  const pft_dd m = {c, d};
-  const pft_dd m2 = dd_mul(m, m), m4 = dd_mul(m2, m2), m5 = dd_mul(m4, m);
-  // T = m5 (1 - k): m5.hi - m5.hi k + m5.lo
-  const double corr = -(m5.hi * k) + m5.lo;
-  const double s = x - m5.hi;                 // exact when x and m5.hi are close (Sterbenz)
-  const double r = s - corr;
-  return r > 0.0 ? 1 : (r < 0.0 ? -1 : 0);
-}
-// c: a candidate within 1 ulp of x^0.2 (ocml's pow on the device)
-__host__ __device__ __forceinline__ double pow02_fix(double x, double c)
-{
-  if (!(x > 0x1p-900 && x < 0x1p900) || !(c > 0.0 && c < 0x1p200)) return c;
-  const double k = 25.0 * (0x1p-54 / 5.0) * log(c);
-  const double up = nextafter(c, INFINITY), dn = nextafter(c, 0.0);
-  if (pow02_side(x, c, 0.5 * (up - c), k) > 0) return up;
-  if (pow02_side(x, c, 0.5 * (dn - c), k) < 0) return dn;
-  return c;
-}
-__device__ __forceinline__ double pow02_rn(double x) { return pow02_fix(x, pow(x, 0.2)); }
-
-// One thread: the step-size control of hybrid2.c:578-611 (rk_solver.c run_fused_impl restates it
-// on the host) for the step (t, h) whose error norm bits epsb / non-finite flag nf were just
-// reduced: the next step's (t, h) when it is accepted, a skip when it is rejected or hit a NaN.
-// pow is the only operation not correctly rounded by IEEE: pow02_rn here, glibc on the host,
-// which agree but for glibc's rare misrounded cases; the host takes its own decision and keeps
-// the gated step only if both agree bit for bit (otherwise it discards it and launches the step
-// again with its own h).
+// One thread: the host loops' own judgement and advance (pft_stepctl.h) of the step (t, h) whose error
+// norm bits epsb / flag nf were just reduced: the next (t, h) if accepted, else a skip.  Only x^0.2 can
+// differ from the host's (pft_stepctl_pow02), which keeps the gated step only if both agree bit for bit.
 __device__ __forceinline__ void gate_decide(const StageArgs& a, double t, double h, unsigned long long epsb, int nf,
                                             bool have_eps)
 {
-  double eps = __longlong_as_double((long long)epsb);
+  const double eps = __longlong_as_double((long long)epsb);
   unsigned long long v = a.gdec_seq | PFT_GATE_SKIP, tb = 0, hb = 0;
-  if (have_eps && !(a.d_nan && nf)) {                                      // :493-503
-    const double h3 = h / 3.0;
-    if (a.d_local) eps *= fabs(h3);                                        // :578
-    const double new_h = ((eps > 0.0) ? pow02_rn((a.d_delta / eps)) * 0.8 : 2.0) * h;   // :580
-    if (eps < a.d_delta || fabs(h) < a.d_hmin) {                           // :599-611
-      const double tn = t + h;                                             // :652
-      const double hn = (fabs(a.d_final - tn) <= fabs(new_h)) ? a.d_final - tn : new_h;   // :743-761
-      tb = (unsigned long long)__double_as_longlong(tn);
-      hb = (unsigned long long)__double_as_longlong(hn);
+  if (have_eps) {
+    // (no command is pending: the host enqueues nothing behind a step that ends the solve)
+    const pft_step at = {t, h, 0};
+    double new_h;
+    const int command = pft_stepctl_judge(a.k, at, eps, nf, &new_h);
+    if (pft_stepctl_accepted(command)) {
+      const pft_step s = pft_stepctl_advance(a.k, at, command, new_h);
+      tb = (unsigned long long)__double_as_longlong(s.t);
+      hb = (unsigned long long)__double_as_longlong(s.h);
       if (a.d_flip > 0 && a.gdec_seq % (unsigned long long)a.d_flip == 0) hb ^= 1ULL;
       v = a.gdec_seq;
     }
@@ -3083,8 +3023,7 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
   a.T_top = t_stage < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
   a.coef = coef;
   a.h = h;
-  // stage-input coefficients of the recompute path: exactly the solver's h/3.0, h/6.0, h/8.0, h
-  a.cin = stage == 2 ? h / 3.0 : stage == 3 ? h / 6.0 : stage == 4 ? h / 8.0 : h;
+  a.cin = pft_stepctl_stage(stage, 0.0, h).cin;   // the recompute path rebuilds the stage input
   if (kind == KFUSED && in) a.x = in;    // pure RHS / speculative stage 1: the input is the given buffer
   // gl's x(t+h) is x + coef*(0.5*(0.0 + 0.0) + 2.0*0.0) (gl's K's are literal zeros): equal to x
   // bit for bit when coef is finite and no gl value is -0.0 or NaN, which the solver checked at
@@ -3137,11 +3076,7 @@ static int run_stage(pft_slab* s, int stage, const double* in, double* kout, dou
     a.gdec_seq = s->gate_arm_seq;
     a.dt = s->gate_arm_t;
     a.dh = s->gate_arm_h;
-    a.d_final = s->gate_final;
-    a.d_delta = s->gate_delta;
-    a.d_hmin = s->gate_hmin;
-    a.d_local = s->gate_local;
-    a.d_nan = s->gate_nan;
+    a.k = s->gate_k;
     a.d_flip = s->gate_flip;
     __atomic_store_n(&s->gate_pin[4 * j], 0ULL, __ATOMIC_RELEASE);   // no decision yet
     s->gate_arm_seq = 0;
@@ -3596,11 +3531,7 @@ double pft_pow02_fix(double x, double c) { return pow02_fix(x, c); }
 
 int pft_slab_gate_config(pft_slab* s, double final_time, double delta, double h_min, int delta_local, int handle_nan)
 {
-  s->gate_final = final_time;
-  s->gate_delta = delta;
-  s->gate_hmin = h_min;
-  s->gate_local = delta_local ? 1 : 0;
-  s->gate_nan = handle_nan ? 1 : 0;
+  s->gate_k = pft_stepctl_consts{final_time, delta, h_min, delta_local, handle_nan};
   return 0;
 }
 
@@ -3830,9 +3761,8 @@ static int run_pair(pft_slab* s, int first, double t_a, double t_b, double h, do
   const long nwg = (long)a.nbw + (long)a.nint;   // the launch's workgroups
   a.T_topA = t_a < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
   a.T_topB = t_b < s->c.phase_switch_time ? s->c.top_temp1 : s->c.top_temp2;
-  // exactly the solver's h/3.0, h/6.0 and h/8.0 (and run_stage's stage-input coefficients)
-  a.cinA = first == 2 ? h / 3.0 : h / 8.0;
-  a.cinB = first == 2 ? h / 6.0 : h;
+  a.cinA = pft_stepctl_stage(first, 0.0, h).cin;   // run_stage's stage-input coefficients
+  a.cinB = pft_stepctl_stage(first + 1, 0.0, h).cin;
   a.coef = coef;
   a.em0 = s->d.eps_mult[0];
   a.em1 = s->d.eps_mult[1];

@@ -22,6 +22,7 @@
 #include "../../include/pft_frontend.h"
 #include "../../include/pft_hip.h"
 #include "../../include/pft_io.h"
+#include "pft_stepctl.h"
 
 #pragma clang fp contract(off)
 
@@ -165,8 +166,7 @@ struct pft_slab {
   unsigned long long gate_arm_seq;   // the next speculative stage-1 launch decides this step ...
   double gate_arm_t, gate_arm_h;     // ... (t, h) of it (ignored when that launch is gated itself)
   unsigned long long gate_use_seq;   // launches enqueued now are gated on this decision (0: not)
-  double gate_final, gate_delta, gate_hmin;   // the solve's constants (pft_slab_gate_config)
-  int gate_local, gate_nan;
+  pft_stepctl_consts gate_k;         // the solve's constants (pft_slab_gate_config)
   int gate_flip;         // test hook, env PFT_GATE_FLIP (StageArgs::d_flip)
   // eps-publication bookkeeping snapshots (pft_slab_book_save/load): the launches of the next
   // step are enqueued between this step's launches and the read of its error norm

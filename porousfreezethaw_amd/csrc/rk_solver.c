@@ -19,6 +19,7 @@
  * Solver state is per host thread (the reference's is per MPI process: one static instance).
  */
 #include "pft_internal.h"
+#include "pft_stepctl.h"
 #include "../../include/pft_frontend.h"
 #include "../../include/pft_formula.h"
 #include "../../include/pft_hist.h"
@@ -253,19 +254,18 @@ static int canonical_chunks(const RK_MEM_DIST * n, double em[3])
 	return R.max_n >= PFT_VAR_COUNT*S;
 }
 
-/* what place() launches: one stage of the step on this slab (stage 1..5; 6 = the speculative stage 1
-   of the next step, K1' = f(ts, XN) into A1, pft_slab_stage_spec), or stages first, first+1 (2+3 or
-   4+5) as ONE pair kernel (pft_slab_pair; stage times ts, tb) */
-typedef struct {
-	int stage, first;
-	double ts, tb, coef, h;
-} launch_what;
+/* what place() launches: one stage of the step (t, h) on this slab (stage 1..5; 6 = the speculative
+   stage 1 of the next step, K1' = f(t+h, XN) into A1, pft_slab_stage_spec), or stages first, first+1 (2+3
+   or 4+5) as ONE pair kernel (pft_slab_pair); the scalars are the step controller's */
+typedef struct { int stage, first; double t, h; } launch_what;
 
 static int run1(const launch_what * w, int kb, int ke)
 {
-	if(w->first) return pft_slab_pair_range(R.slab, w->first, w->ts, w->tb, w->h, w->coef, kb, ke);
-	return w->stage == 6 ? pft_slab_stage_spec(R.slab, w->ts, kb, ke)
-	                     : pft_slab_stage(R.slab, w->stage, w->ts, w->coef, w->h, kb, ke);
+	const pft_stage_scalars s = pft_stepctl_stage(w->first ? w->first : w->stage, w->t, w->h);
+	if(w->first)   /* (coef: x(t+h)'s, stage 5's, for either pair, as the pair kernel takes it) */
+		return pft_slab_pair_range(R.slab, w->first, s.ts, pft_stepctl_stage(w->first+1, w->t, w->h).ts, w->h,
+		                           pft_stepctl_stage(5, w->t, w->h).coef, kb, ke);
+	return w->stage == 6 ? pft_slab_stage_spec(R.slab, s.ts, kb, ke) : pft_slab_stage(R.slab, w->stage, s.ts, s.coef, w->h, kb, ke);
 }
 
 /* a launch and the exchange of its output's boundary planes (nfields fields of out_buf), timed as
@@ -312,17 +312,17 @@ static int place(const launch_what * w, int out_buf, int nfields, int tstage, lo
 	return 0;
 }
 
-static int do_stage(int stage, double ts, double coef, double h, long * launches)
+static int do_stage(int stage, double t, double h, long * launches)
 {
-	const launch_what w = {stage, 0, ts, 0.0, coef, h};
+	const launch_what w = {stage, 0, t, h};
 	return place(&w, stage == 6 ? PFT_BUF_A1 : pft_slab_stage_output(R.slab, stage),
 	             pft_slab_stage_fields(R.slab, stage), stage == 6 ? 1 : stage, launches);
 }
 
 /* timed as stage first+1 */
-static int do_pair(int first, double ta, double tb, double h, double coef, long * launches)
+static int do_pair(int first, double t, double h, long * launches)
 {
-	const launch_what w = {0, first, ta, tb, coef, h};
+	const launch_what w = {0, first, t, h};
 	return place(&w, first == 2 ? PFT_BUF_K3 : PFT_BUF_XN, pft_slab_stage_fields(R.slab, first+1), first+1, launches);
 }
 
@@ -348,14 +348,69 @@ static int gl_clean(const double * x)
 	return !bad;
 }
 
-/* shared prologue results */
-typedef struct {
-	double final_time, t, h, h_min, delta;
-	int delta_mode, handle_nan, any_cb;
-} solve_bcast;
+/* shared prologue results: the solve's constants and the attempt under way (t, h, the pending command) */
+typedef struct { pft_stepctl_consts k; pft_step a; int any_cb; } solve_bcast;
 
-static int run_staged(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast * B, int command,
-                      long max_steps_total, int flags);
+static int run_staged(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast * B, long max_steps_total, int flags);
+
+/* What run_fused and run_staged share around the step controller (pft_stepctl.h): a loop computes the attempt
+   B->a its own way, then step_judge, if accepted its own accept action and step_accepted, then step_next */
+typedef struct {
+	RK_MPI_S_SOLUTION * system;
+	solve_bcast * B;
+	long max_steps, attempted;
+	int command, ret;     /* the attempt as judged, with new_h; the call's return code once a routine ends the loop */
+	double new_h;
+} step_loop;
+
+/* count and judge the attempt, its error norm known; 1: the solve ends here (-4) */
+static int step_judge(step_loop * L, double eps, int nonfinite)
+{
+	L->system->steps_total++;                                                /* :460 */
+	L->attempted++;
+	R.stats.last_eps = eps;                                                  /* unscaled by DELTA_LOCAL */
+	L->command = pft_stepctl_judge(L->B->k, L->B->a, eps, nonfinite, &L->new_h);
+	if(L->command & RKA_CMD_NAN) R.last_nan = 1;                             /* :626-646 */
+	if((L->command & RKA_CMD_NAN) && (L->command & RKA_CMD_h_TOO_SMALL)) L->ret = -4;
+	return L->ret == -4;
+}
+
+/* accepted, x is x(t+h) (resident: on the device): B->a advances; callback, broadcast, FINISHED and BREAK.
+   1: the solve ends here; negative: a collective failed */
+static int step_accepted(step_loop * L, int resident)
+{
+	RK_MPI_S_SOLUTION * system = L->system;
+	const double h = L->B->a.h;
+	int rc;
+	L->B->a = pft_stepctl_advance(L->B->k, L->B->a, L->command, L->new_h);
+	system->steps++;
+	if(system->Service_Callback != NULL) {                                   /* :676-685 */
+		system->t = L->B->a.t;
+		system->h = h;
+		R.in_callback = resident;            /* a callback that reads x calls pft_solver_download first */
+		if(system->Service_Callback(L->B->k.final_time, system)) L->command |= RKA_CMD_BREAK;
+		R.in_callback = 0;
+	}
+	if(pft_comm_size(comm()) > 1 && L->B->any_cb && (rc = pft_comm_bcast(comm(), &L->command, sizeof(int), R.master)))
+		return rc;                                                           /* :690 */
+	if(L->command & RKA_CMD_FINISHED) return 1;                              /* :695 */
+	if(!(L->command & RKA_CMD_BREAK)) return 0;
+	system->h = L->new_h;                                                    /* :697-705 */
+	L->ret = 1;
+	return 1;
+}
+
+/* on to the next attempt (:743-761; an accepted one has advanced).  1: the step cap (an extension) ends the
+   call between two attempts; the next call's prologue re-derives FINISHED from t, h */
+static int step_next(step_loop * L)
+{
+	if(!pft_stepctl_accepted(L->command)) L->B->a = pft_stepctl_advance(L->B->k, L->B->a, L->command, L->new_h);
+	else if(L->command & RKA_CMD_NEXTFINISH) L->system->h = L->new_h;
+	if(!(L->max_steps > 0 && L->attempted >= L->max_steps)) return 0;
+	L->system->h = L->B->a.h;
+	L->ret = 2;
+	return 1;
+}
 
 /* PFT_GATE_TRACE=1: host-side timeline of the gated pipeline (stderr at the end of a call) */
 static double gt_now(void)
@@ -365,15 +420,15 @@ static double gt_now(void)
 	return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
 }
 
-static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast * B, int command,
-                     long max_steps_total, int flags, const double * em)
+static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast * B, long max_steps_total,
+                     int flags, const double * em)
 {
 	pft_comm * c = comm();
-	const int rank = pft_comm_rank(c), nprocs = pft_comm_size(c);
-	double t = B->t, h = B->h, new_h = 0.0, h2, h3, h6, h8, eps;
-	const double final_time = B->final_time, delta = B->delta, h_min = B->h_min;
-	int nonfinite, rc, ret = 0, to_host = 0;
-	long attempted = 0, launches = 0;
+	const int nprocs = pft_comm_size(c);
+	step_loop L = {system, B, max_steps_total};
+	double eps;
+	int nonfinite, rc, st, to_host = 0;
+	long launches = 0;
 	int spec, k1_valid = 0;               /* K1 holds f(t, x) for the current t and x */
 	int pair;                             /* stages 2+3 and 4+5 as pair kernels */
 	int gate, pre = 0, acc, enq;          /* gated steps; this attempt was pre-enqueued; accepted;
@@ -407,7 +462,7 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 		   and XN).  Every rank takes the same decision (the same calls, flags and t). */
 		pft_consts cc;
 		if(spec && (flags & PFT_SOLVE_REUSE_DEVICE) && R.device_valid && R.k1_keep && R.k1_slab == R.slab &&
-		   (!R.deep || R.k1_deep) && !pft_model_noise() && memcmp(&R.k1_t, &t, sizeof t) == 0 && !pft_model_get_consts(&cc) &&
+		   (!R.deep || R.k1_deep) && !pft_model_noise() && memcmp(&R.k1_t, &B->a.t, sizeof R.k1_t) == 0 && !pft_model_get_consts(&cc) &&
 		   memcmp(&cc, &R.k1_c, sizeof cc) == 0)
 			k1_valid = 1;
 		R.k1_keep = 0;
@@ -450,9 +505,9 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 	/* f4, gated steps (PFT_OPT_GATE, pft_slab_gate_*): on one slab with one launch per stage, the
 	   next attempted step's launches are enqueued before this step's error norm is read, as if the
 	   step were accepted.  This step's speculative stage 1 reduces the error norm and decides the
-	   step on the device (hybrid2.c:578-611, the expressions below); the gated launches run on
+	   step on the device (the controller of pft_stepctl.h, as step_judge here); the gated launches run on
 	   that decision, so the GPU waits neither for the host's round trip nor for its launch latency.
-	   The host still takes the decision below (glibc pow) and keeps the gated step only if the
+	   The host still takes its own decision (glibc pow) and keeps the gated step only if the
 	   device's (ocml pow) is the same bit for bit; otherwise that step is discarded -- it wrote only
 	   buffers nothing reads afterwards (XN, A0, K3, K4, A1) -- and launched again.  Not with a
 	   Service_Callback (it may read x between steps) or per-stage timing. */
@@ -463,38 +518,36 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 	}
 	gate = gate && spec && !pair && nprocs == 1 && !pft_comm_splits(c) &&
 	       system->Service_Callback == NULL && !R.opt_timing;
-	if(gate) pft_slab_gate_config(R.slab, final_time, delta, h_min, B->delta_mode == DELTA_LOCAL, B->handle_nan);
+	if(gate) pft_slab_gate_config(R.slab, B->k.final_time, B->k.delta, B->k.h_min, B->k.delta_local, B->k.handle_nan);
 	const int gtrace = getenv("PFT_GATE_TRACE") != NULL;
 	double gt_t0 = 0.0, gt_enq = 0.0, gt_wait = 0.0, gt_dec = 0.0, gt_a, gt_b;
 	long gt_n = 0;
 	if(gtrace) gt_t0 = gt_now();
 
 	while(1) {
-		h2 = h/2.0; h3 = h/3.0; h6 = h/6.0; h8 = h/8.0;                          /* :355 */
-		R.tstep = R.opt_timing > 0 && attempted % R.opt_timing == 0;
+		const double t = B->a.t, h = B->a.h;
+		R.tstep = R.opt_timing > 0 && L.attempted % R.opt_timing == 0;
 		acc = 0;
 		if(!pre) {
 			/* the error norm accumulator is reset by its publication on the speculative path */
-			if((!spec || attempted == 0) && (rc = pft_slab_eps_reset(R.slab))) return rc;
+			if((!spec || L.attempted == 0) && (rc = pft_slab_eps_reset(R.slab))) return rc;
 			/* K1 = f(t,x); aux = x + K1 h/3 ... K5 = f(t+h, aux); error norm; x(t+h) candidate */
 			if(pair) {
 				/* the same arithmetic: stage A of each pair is evaluated inside stage B's stencil */
-				if(!k1_valid && (rc = do_stage(1, t, h3, h, &launches))) return rc;      /* :373-389 */
-				if((rc = do_pair(2, t+h3, t+h3, h, h3, &launches))) return rc;          /* :392-429 */
-				if((rc = do_pair(4, t+h2, t+h, h, h3, &launches))) return rc;           /* :432-524,657-668 */
+				if(!k1_valid && (rc = do_stage(1, t, h, &launches))) return rc;          /* :373-389 */
+				if((rc = do_pair(2, t, h, &launches))) return rc;                        /* :392-429 */
+				if((rc = do_pair(4, t, h, &launches))) return rc;                        /* :432-524,657-668 */
 			} else {
-				if(!(spec && k1_valid) && (rc = do_stage(1, t, h3, h, &launches))) return rc;  /* :373-389 */
-				if((rc = do_stage(2, t+h3, h6, h, &launches))) return rc;    /* :392-409 */
-				if((rc = do_stage(3, t+h3, h8, h, &launches))) return rc;    /* :412-429 */
-				if((rc = do_stage(4, t+h2, h,  h, &launches))) return rc;    /* :432-450 */
-				if((rc = do_stage(5, t+h,  h3, h, &launches))) return rc;    /* :453,507-524,657-668 */
+				if(!(spec && k1_valid) && (rc = do_stage(1, t, h, &launches))) return rc;  /* :373-389 */
+				for(st = 2; st <= 5; st++)                                   /* :392-453,507-524,657-668 */
+					if((rc = do_stage(st, t, h, &launches))) return rc;
 			}
 			k1_valid = 1;
 			if(spec) {
 				/* eps max over ranks (:572) and its publication beside the speculative stage 1 */
 				if((rc = pft_comm_eps_publish(c))) return rc;
 				if(gate) gcur = pft_slab_gate_arm(R.slab, t, h);
-				if((rc = do_stage(6, t+h, 0.0, h, &launches))) return rc;
+				if((rc = do_stage(6, t, h, &launches))) return rc;
 			} else {
 				/* the boundary launch of stage 5 (comm stream) adds to the error norm too */
 				if(pft_comm_splits(c) && (rc = pft_slab_order(R.slab, 1))) return rc;
@@ -506,8 +559,8 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 		gt_a = gtrace ? gt_now() : 0.0;
 		/* pre-enqueue the next attempt unless this one ends the solve if accepted (FINISHED) or the
 		   step cap stops before it */
-		enq = gate && gcur && !(command & RKA_CMD_FINISHED) &&
-		      !(max_steps_total > 0 && attempted + 1 >= max_steps_total);
+		enq = gate && gcur && !(B->a.command & RKA_CMD_FINISHED) &&
+		      !(max_steps_total > 0 && L.attempted + 1 >= max_steps_total);
 		if(enq) {
 			/* the next attempted step, enqueued now as if this one were accepted (the buffers
 			   swapped as the accept below swaps them, for the enqueue only): stages 2-5 and its
@@ -517,14 +570,10 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 			pft_slab_accept(R.slab);
 			pft_slab_swap_buffers(R.slab, PFT_BUF_K1, PFT_BUF_A1);
 			pft_slab_gate_use(R.slab, gcur);
-			rc = 0;
-			if(!rc) rc = do_stage(2, 0.0, 0.0, 0.0, &launches);
-			if(!rc) rc = do_stage(3, 0.0, 0.0, 0.0, &launches);
-			if(!rc) rc = do_stage(4, 0.0, 0.0, 0.0, &launches);
-			if(!rc) rc = do_stage(5, 0.0, 0.0, 0.0, &launches);
+			for(rc = 0, st = 2; st <= 5 && !rc; st++) rc = do_stage(st, 0.0, 0.0, &launches);
 			if(!rc) rc = pft_comm_eps_publish(c);
 			if(!rc) gnext = pft_slab_gate_arm(R.slab, 0.0, 0.0);   /* (t, h) from its own gate */
-			if(!rc) rc = do_stage(6, 0.0, 0.0, 0.0, &launches);
+			if(!rc) rc = do_stage(6, 0.0, 0.0, &launches);
 			pft_slab_gate_use(R.slab, 0);
 			pft_slab_accept(R.slab);
 			pft_slab_swap_buffers(R.slab, PFT_BUF_K1, PFT_BUF_A1);
@@ -543,72 +592,20 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 		}
 		if((rc = pft_comm_eps_host(c, &eps, &nonfinite))) return rc;                 /* :572 (ipc) */
 		if(R.opt_timing) pft_slab_timing_collect(R.slab, R.stats.stage_ms, R.stats.stage_n);
-		system->steps_total++;                                                   /* :460 */
-		attempted++;
-		R.stats.last_eps = eps;
-
-		if(B->handle_nan && nonfinite) {                                         /* :493-503 */
-			command |= RKA_CMD_NAN;
-			if(h/(final_time-t) < 1e-11) command |= RKA_CMD_h_TOO_SMALL;
+		if(step_judge(&L, eps, nonfinite)) break;
+		if(pft_stepctl_accepted(L.command)) {                                             /* :651-668 */
+			acc = 1;
+			pft_slab_accept(R.slab);
+			if(spec) pft_slab_swap_buffers(R.slab, PFT_BUF_K1, PFT_BUF_A1);      /* K1 = f(t, x) */
+			else k1_valid = 0;
+			if((rc = step_accepted(&L, 1)) < 0) return rc;
+			if(rc) break;
+			f = system->meta_f();                                                /* :732 */
+			/* another right-hand side from the next step on: the state leaves the device
+			   and the loop continues on the host-staged path (below) */
+			if(!pft_model_is_device_rhs(f)) to_host = 1;
 		}
-		if(B->delta_mode == DELTA_LOCAL) eps *= fabs(h3);                        /* :578 */
-		new_h = ((eps > 0.0) ? pow((delta/eps), 0.2)*0.8 : 2.0) * h;            /* :580 */
-		if(eps < delta || fabs(h) < h_min) {                                     /* :599-611 */
-			command |= RKA_CMD_UPDATE;
-			if(fabs(final_time-(t+h)) <= fabs(new_h)) command |= RKA_CMD_NEXTFINISH;
-		}
-
-		if(command & RKA_CMD_NAN) {                                              /* :626-646 */
-			R.last_nan = 1;
-			if(command & RKA_CMD_h_TOO_SMALL) { system->t = t; ret = -4; break; }
-			h /= 10;
-			command = 0;
-		} else {
-			if(command & RKA_CMD_UPDATE) {                                       /* :651-668 */
-				t += h;
-				acc = 1;
-				pft_slab_accept(R.slab);
-				if(spec) pft_slab_swap_buffers(R.slab, PFT_BUF_K1, PFT_BUF_A1);  /* K1 = f(t, x) */
-				else k1_valid = 0;
-				system->steps++;
-				if(system->Service_Callback != NULL) {                           /* :676-685 */
-					/* x stays on the device: a callback that reads it calls
-					   pft_solver_download(system) first (pft_solver.h) */
-					system->t = t;
-					system->h = h;
-					R.in_callback = 1;
-					if(system->Service_Callback(final_time, system)) command |= RKA_CMD_BREAK;
-					R.in_callback = 0;
-				}
-				if(nprocs > 1 && B->any_cb && (rc = pft_comm_bcast(c, &command, sizeof(int), R.master))) return rc;   /* :690 */
-				if(command & RKA_CMD_FINISHED) break;                            /* :695 */
-				if(command & RKA_CMD_BREAK) {                                    /* :697-705 */
-					system->t = t;
-					system->h = new_h;
-					ret = 1;
-					break;
-				}
-				f = system->meta_f();                                            /* :732 */
-				/* another right-hand side from the next step on: the state leaves the device
-				   and the loop continues on the host-staged path (below) */
-				if(!pft_model_is_device_rhs(f)) to_host = 1;
-			}
-			if(command & RKA_CMD_NEXTFINISH) {                                   /* :743-761 */
-				system->h = new_h;
-				h = final_time - t;
-				command = RKA_CMD_FINISHED;
-			} else {
-				command = 0;
-				h = new_h;
-			}
-		}
-		if(max_steps_total > 0 && attempted >= max_steps_total) {
-			/* extension: stop between two attempted steps; the next call continues the
-			   identical trajectory (its prologue re-derives FINISHED from t, h) */
-			system->h = h;
-			ret = 2;
-			break;
-		}
+		if(step_next(&L)) break;
 		if(to_host) break;
 		if(enq) {
 			/* keep the pre-enqueued attempt iff the device took this decision, bit for bit:
@@ -618,7 +615,7 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 			double td = 0.0, hd = 0.0;
 			if((rc = pft_slab_gate_decision(R.slab, gcur, &go, &td, &hd))) return rc;
 			if(gtrace) gt_dec += gt_now() - gt_a;
-			if(acc && go && memcmp(&td, &t, sizeof t) == 0 && memcmp(&hd, &h, sizeof h) == 0) {
+			if(acc && go && memcmp(&td, &B->a.t, sizeof td) == 0 && memcmp(&hd, &B->a.h, sizeof hd) == 0) {
 				pft_slab_book_load(R.slab, 1);
 				pre = 1;
 				R.stats.gated_steps++;
@@ -635,14 +632,13 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 		fprintf(stderr, "libpft gate trace: %ld attempts, %.2f us each: enqueue %.2f, eps wait %.2f, "
 		        "decide+compare %.2f (gated %ld, pow misses %ld)\n", gt_n, (gt_now() - gt_t0) / gt_n,
 		        gt_enq / gt_n, gt_wait / gt_n, gt_dec / gt_n, R.stats.gated_steps, R.stats.gate_misses);
-	(void)rank;
 	/* join the comm stream (the last boundary launch and exchange) before the state leaves */
 	if(pft_comm_splits(c) && (rc = pft_slab_order(R.slab, 1))) return rc;
-	if(ret != 1 && ret != -4) system->t = t;                                     /* :768 */
-	if(spec && k1_valid && ret != -4 && !to_host && !pft_model_get_consts(&R.k1_c)) {
+	system->t = B->a.t;                                                             /* :768 */
+	if(spec && k1_valid && L.ret != -4 && !to_host && !pft_model_get_consts(&R.k1_c)) {
 		/* K1 = f(t, x) for the state this call leaves on the device (see R.k1_keep) */
 		R.k1_keep = 1;
-		R.k1_t = t;
+		R.k1_t = B->a.t;
 		R.k1_slab = R.slab;
 		R.k1_deep = R.deep;
 	}
@@ -650,23 +646,20 @@ static int run_fused(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast
 	R.tstep = 0;
 	R.device_valid = 1;
 	R.stats.kernel_launches = launches;
-	R.stats.steps_total = attempted;
+	R.stats.steps_total = L.attempted;
 	if(!(flags & PFT_SOLVE_KEEP_DEVICE) || to_host) {
 		if((rc = pft_slab_download_host(R.slab, PFT_BUF_X, system->x))) return rc;
 	}
 	if(to_host) {
-		/* meta_f() returned a right-hand side that is not libpft's: carry on from t, h and the
-		   pending command with it, on the host-staged path (hybrid2.c:732 keeps integrating with
-		   the new f) -- unless the step cap ended this call on that very step: then it returns 2
-		   like any capped call, and the next call (its prologue calls meta_f()) takes the
-		   host-staged path from the start */
+		/* meta_f() returned a right-hand side that is not libpft's: carry on from the attempt B->a with it
+		   on the host-staged path (hybrid2.c:732 keeps integrating with the new f) -- unless the step cap
+		   ended this call on that very step: then it returns 2 like any capped call, and the next call (its
+		   prologue calls meta_f()) takes the host-staged path from the start */
 		R.device_valid = 0;
-		if(ret == 2) return ret;
-		B->t = t;
-		B->h = h;
-		return run_staged(system, f, B, command, max_steps_total > 0 ? max_steps_total - attempted : 0, flags);
+		if(L.ret == 2) return L.ret;
+		return run_staged(system, f, B, max_steps_total > 0 ? max_steps_total - L.attempted : 0, flags);
 	}
-	return ret;
+	return L.ret;
 }
 
 int pft_solver_download(RK_MPI_S_SOLUTION * system)
@@ -1389,18 +1382,16 @@ static int staged_rhs(RK_RightHandSide f, double t, const double * d_in, double 
 	return 0;
 }
 
-static int run_staged(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast * B, int command,
-                      long max_steps_total, int flags)
+static int run_staged(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcast * B, long max_steps_total, int flags)
 {
 	R.k1_keep = 0;                       /* this path computes K1 in the slab's buffers */
 	pft_comm * c = comm();
 	const int nprocs = pft_comm_size(c);
 	RK_MEM_DIST * n = system->n;
 	double * x = system->x;
-	double t = B->t, h = B->h, new_h = 0.0, h2, h3, h6, h8, eps;
-	const double final_time = B->final_time, delta = B->delta, h_min = B->h_min;
-	int rc, ret = 0, nch = n->n_chunks;
-	long attempted = 0;
+	step_loop L = {system, B, max_steps_total};
+	double eps;
+	int rc, nch = n->n_chunks;
 	double zero2[2] = {0.0, 0.0};
 	(void)flags;
 
@@ -1409,24 +1400,18 @@ static int run_staged(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcas
 	R.stats.path = 2;
 
 	while(1) {
+		const double t = B->a.t, h = B->a.h;
+		double * const kbuf[6] = {NULL, R.d_k1, R.d_k3, R.d_k3, R.d_k4, R.d_k5};   /* K2 in K3's buffer */
 		long long bits[2];
-		h2 = h/2.0; h3 = h/3.0; h6 = h/6.0; h8 = h/8.0;
-		if((rc = staged_rhs(f, t, NULL, x, R.d_k1))) return rc;                                   /* :373 */
-		if((rc = pft_flat_combine(1, nch, R.d_cs, R.d_cz, R.d_cm, h3, h, R.d_x, R.d_k1, R.d_k3, R.d_k3,
-		                          R.d_k4, R.d_k5, R.d_aux, R.d_eps, NULL))) return rc;          /* :378-389 */
-		if((rc = staged_rhs(f, t+h3, R.d_aux, R.h_aux, R.d_k3))) return rc;                       /* K2 in K3, :392 */
-		if((rc = pft_flat_combine(2, nch, R.d_cs, R.d_cz, R.d_cm, h6, h, R.d_x, R.d_k1, R.d_k3, R.d_k3,
-		                          R.d_k4, R.d_k5, R.d_aux, R.d_eps, NULL))) return rc;          /* :397-409 */
-		if((rc = staged_rhs(f, t+h3, R.d_aux, R.h_aux, R.d_k3))) return rc;                       /* :412 */
-		if((rc = pft_flat_combine(3, nch, R.d_cs, R.d_cz, R.d_cm, h8, h, R.d_x, R.d_k1, R.d_k3, R.d_k3,
-		                          R.d_k4, R.d_k5, R.d_aux, R.d_eps, NULL))) return rc;          /* :417-429 */
-		if((rc = staged_rhs(f, t+h2, R.d_aux, R.h_aux, R.d_k4))) return rc;                       /* :432 */
-		if((rc = pft_flat_combine(4, nch, R.d_cs, R.d_cz, R.d_cm, h, h, R.d_x, R.d_k1, R.d_k3, R.d_k3,
-		                          R.d_k4, R.d_k5, R.d_aux, R.d_eps, NULL))) return rc;          /* :437-450 */
-		if((rc = staged_rhs(f, t+h, R.d_aux, R.h_aux, R.d_k5))) return rc;                        /* :453 */
-		if((rc = pft_flat_h2d(R.d_eps, zero2, 2, NULL))) return rc;
-		if((rc = pft_flat_combine(5, nch, R.d_cs, R.d_cz, R.d_cm, h3, h, R.d_x, R.d_k1, R.d_k3, R.d_k3,
-		                          R.d_k4, R.d_k5, R.d_aux, R.d_eps, NULL))) return rc;          /* :507-524 */
+		int st;
+		for(st = 1; st <= 5; st++) {
+			/* K = f(ts, stage input), then the stage's combine into aux, stage 5's into the error norm (:373-453, 507-524) */
+			const pft_stage_scalars s = pft_stepctl_stage(st, t, h);
+			if((rc = staged_rhs(f, s.ts, st == 1 ? NULL : R.d_aux, st == 1 ? x : R.h_aux, kbuf[st]))) return rc;
+			if(st == 5 && (rc = pft_flat_h2d(R.d_eps, zero2, 2, NULL))) return rc;
+			if((rc = pft_flat_combine(st, nch, R.d_cs, R.d_cz, R.d_cm, s.coef, h, R.d_x, R.d_k1, R.d_k3, R.d_k3,
+			                          R.d_k4, R.d_k5, R.d_aux, R.d_eps, NULL))) return rc;
+		}
 		if((rc = pft_flat_d2h((double*)bits, R.d_eps, 2, NULL)) || (rc = pft_stream_sync(NULL))) return rc;
 		if(nprocs > 1) {
 			if((rc = pft_comm_allreduce_max_i64(c, &bits[0]))) return rc;                      /* :572 */
@@ -1434,69 +1419,32 @@ static int run_staged(RK_MPI_S_SOLUTION * system, RK_RightHandSide f, solve_bcas
 			if((rc = pft_comm_allreduce_max_i64(c, &bits[1]))) return rc;
 		}
 		memcpy(&eps, &bits[0], sizeof(double));
-		system->steps_total++;
-		attempted++;
-		R.stats.last_eps = eps;
-		if(B->handle_nan && (bits[1] & 0xffffffffLL)) {
-			command |= RKA_CMD_NAN;
-			if(h/(final_time-t) < 1e-11) command |= RKA_CMD_h_TOO_SMALL;
-		}
-		if(B->delta_mode == DELTA_LOCAL) eps *= fabs(h3);
-		new_h = ((eps > 0.0) ? pow((delta/eps), 0.2)*0.8 : 2.0) * h;
-		if(eps < delta || fabs(h) < h_min) {
-			command |= RKA_CMD_UPDATE;
-			if(fabs(final_time-(t+h)) <= fabs(new_h)) command |= RKA_CMD_NEXTFINISH;
-		}
-		if(command & RKA_CMD_NAN) {
-			R.last_nan = 1;
-			if(command & RKA_CMD_h_TOO_SMALL) { system->t = t; ret = -4; break; }
-			h /= 10;
-			command = 0;
-		} else {
-			if(command & RKA_CMD_UPDATE) {
-				t += h;
-				if((rc = pft_flat_combine(6, nch, R.d_cs, R.d_cz, R.d_cm, h3, h, R.d_x, R.d_k1, R.d_k3, R.d_k3,
-				                          R.d_k4, R.d_k5, R.d_x, R.d_eps, NULL))) return rc;    /* :657-668 */
-				/* the right-hand side of the next step reads the host x: only the chunks (the
-				   unknowns) come back, the ghost values the last f(t, x) wrote stay (the
-				   reference updates x in place, hybrid2.c:657-668) */
-				if((rc = pft_flat_d2h(R.h_aux, R.d_x, R.max_n, NULL)) || (rc = pft_stream_sync(NULL))) return rc;
-				{
-					int ch;
-					for(ch = 0; ch < nch; ch++)
-						memcpy(x + n->chunk_start[ch], R.h_aux + n->chunk_start[ch], sizeof(double)*n->chunk_size[ch]);
-				}
-				system->steps++;
-				if(system->Service_Callback != NULL) {
-					system->t = t;
-					system->h = h;
-					if(system->Service_Callback(final_time, system)) command |= RKA_CMD_BREAK;
-				}
-				if(nprocs > 1 && B->any_cb && (rc = pft_comm_bcast(c, &command, sizeof(int), R.master))) return rc;
-				if(command & RKA_CMD_FINISHED) break;
-				if(command & RKA_CMD_BREAK) { system->t = t; system->h = new_h; ret = 1; break; }
-				if(system->DDLBF_Rearrange != NULL) {                                              /* :726-729 */
-					n = system->n = system->DDLBF_Rearrange(n);
-					nch = n->n_chunks;
-					if((rc = ensure_staged(n))) return rc;
-				}
-				f = system->meta_f();
+		if(step_judge(&L, eps, (bits[1] & 0xffffffffLL) != 0)) break;
+		if(pft_stepctl_accepted(L.command)) {
+			int ch;
+			if((rc = pft_flat_combine(6, nch, R.d_cs, R.d_cz, R.d_cm, pft_stepctl_stage(5, t, h).coef, h, R.d_x, R.d_k1, R.d_k3,
+			                          R.d_k3, R.d_k4, R.d_k5, R.d_x, R.d_eps, NULL))) return rc;    /* :657-668 */
+			/* the right-hand side of the next step reads the host x: only the chunks (the
+			   unknowns) come back, the ghost values the last f(t, x) wrote stay (the
+			   reference updates x in place, hybrid2.c:657-668) */
+			if((rc = pft_flat_d2h(R.h_aux, R.d_x, R.max_n, NULL)) || (rc = pft_stream_sync(NULL))) return rc;
+			for(ch = 0; ch < nch; ch++)
+				memcpy(x + n->chunk_start[ch], R.h_aux + n->chunk_start[ch], sizeof(double)*n->chunk_size[ch]);
+			if((rc = step_accepted(&L, 0)) < 0) return rc;
+			if(rc) break;
+			if(system->DDLBF_Rearrange != NULL) {                                              /* :726-729 */
+				n = system->n = system->DDLBF_Rearrange(n);
+				nch = n->n_chunks;
+				if((rc = ensure_staged(n))) return rc;
 			}
-			if(command & RKA_CMD_NEXTFINISH) {
-				system->h = new_h;
-				h = final_time - t;
-				command = RKA_CMD_FINISHED;
-			} else {
-				command = 0;
-				h = new_h;
-			}
+			f = system->meta_f();                                                              /* :732 */
 		}
-		if(max_steps_total > 0 && attempted >= max_steps_total) { system->h = h; ret = 2; break; }
+		if(step_next(&L)) break;
 	}
-	if(ret != 1 && ret != -4) system->t = t;
-	R.stats.steps_total = attempted;
-	R.stats.kernel_launches = 6*attempted;
-	return ret;
+	system->t = B->a.t;                                                                           /* :768 */
+	R.stats.steps_total = L.attempted;
+	R.stats.kernel_launches = 6*L.attempted;
+	return L.ret;
 }
 
 /* ---------------------------------------------------------------------------------------- */
@@ -1506,7 +1454,7 @@ int pft_solve_ex(FLOAT final_time, RK_MPI_S_SOLUTION * system, long max_steps_to
 {
 	pft_comm * c = comm();
 	const int rank = pft_comm_rank(c);
-	int error_code = 0, command = 0, crc;
+	int error_code = 0, crc;
 	long long neg;
 	RK_RightHandSide f = NULL;
 	solve_bcast B;
@@ -1528,24 +1476,24 @@ int pft_solve_ex(FLOAT final_time, RK_MPI_S_SOLUTION * system, long max_steps_to
 	if(neg > 0) return -6;                                                      /* :299 */
 
 	R.last_nan = 0;                                                             /* :316 */
-	B.final_time = final_time; B.t = system->t; B.h = system->h;
-	B.h_min = system->h_min; B.delta = system->delta; B.delta_mode = (int)system->delta_mode;
-	B.handle_nan = R.handle_nan;
+	B.k.final_time = final_time; B.k.delta = system->delta; B.k.h_min = system->h_min;
+	B.k.delta_local = system->delta_mode == DELTA_LOCAL; B.k.handle_nan = R.handle_nan;
+	B.a.t = system->t; B.a.h = system->h; B.a.command = 0;
 	B.any_cb = system->Service_Callback != NULL;
 	if(rank == R.master) {                                                      /* :319-325 */
-		if((B.final_time > B.t && B.h < 0) || (B.final_time < B.t && B.h > 0)) B.h *= -1;
-		if(B.h == 0 || fabs(B.final_time - B.t) <= fabs(B.h)) {
-			B.h = B.final_time - B.t;
-			command |= RKA_CMD_FINISHED;
+		if((final_time > B.a.t && B.a.h < 0) || (final_time < B.a.t && B.a.h > 0)) B.a.h *= -1;
+		if(B.a.h == 0 || fabs(final_time - B.a.t) <= fabs(B.a.h)) {
+			B.a.h = final_time - B.a.t;
+			B.a.command |= RKA_CMD_FINISHED;
 		}
 	}
 	if(pft_comm_size(c) > 1) {                                                  /* :328-336 */
-		long long cmd = command;
+		long long cmd = B.a.command;
 		if((crc = pft_comm_bcast(c, &B, sizeof(B), R.master)) || (crc = pft_comm_allreduce_max_i64(c, &cmd))) {
 			R.last_status = crc;
 			return PFT_SOLVE_DEVICE_ERROR;
 		}
-		command = (int)cmd;
+		B.a.command = (int)cmd;
 	}
 	R.stats.nprocs = pft_comm_size(c);
 	R.stats.rank = rank;
@@ -1554,9 +1502,9 @@ int pft_solve_ex(FLOAT final_time, RK_MPI_S_SOLUTION * system, long max_steps_to
 		int rc;
 		double em[3];
 		if(pft_model_is_device_rhs(f) && system->DDLBF_Rearrange == NULL && canonical_chunks(n, em))
-			rc = run_fused(system, f, &B, command, max_steps_total, flags, em);
+			rc = run_fused(system, f, &B, max_steps_total, flags, em);
 		else
-			rc = run_staged(system, f, &B, command, max_steps_total, flags);
+			rc = run_staged(system, f, &B, max_steps_total, flags);
 		/* a HIP or RCCL failure (out of device memory, a lost peer, ...) is reported as
 		   PFT_SOLVE_DEVICE_ERROR; the raw status stays in pft_solver_last_status() and the HIP
 		   text in pft_hip_last_error() */

@@ -638,6 +638,37 @@ def test_epsctl_multipliers_within_a_variable_take_the_staged_path():
     assert np.array_equal(x, A["d_state0"])
 
 
+@pytest.mark.parametrize("name", ["a", "c"])
+def test_epsctl_delta_local_on_the_staged_path(name):
+    """the reference's DELTA_LOCAL runs (a) and (c) under run_staged -- an identity DDLBF_Rearrange
+    keeps the solve off the fused path (hybrid2.c:726-729): the controller's local scaling, and the
+    NEXTFINISH hand-over that ends the solve at T, on the host-staged loop"""
+    meta, A = O.load_case("epsctl")
+    Pm, info = O.params_from_meta(meta)
+    run = meta["runs"][name]
+    assert run["delta_local"]
+    sim = P.Simulation(info["n1"], info["n2"], info["n3"], (info["L1"], info["L2"], info["L3"]), 0, Pm,
+                       initial=A["ic"], tau=run["h0"], t0=run["t0"], tau_min=info["tau_min"], delta=info["delta"],
+                       chunk_mult=run["mult"], delta_mode=P.DELTA_LOCAL)
+
+    @P.REARRANGE_FN
+    def same(n):
+        return n
+
+    sim.system.DDLBF_Rearrange = C.cast(same, C.c_void_p).value
+    try:
+        rc = sim.solve(meta["T"])
+        path = sim.stats().path
+        got = (sim.t.hex(), sim.h.hex(), sim.system.steps, sim.system.steps_total, rc)
+        x = sim.interior()
+    finally:
+        sim.close()
+    ref = run["traj"][0]
+    assert path == 2
+    assert got == (float.fromhex(ref[0]).hex(), float.fromhex(ref[1]).hex(), ref[2], ref[3], ref[4])
+    assert np.array_equal(x, A[f"{name}_state0"])
+
+
 ROUTES = {
     "cache": ((17, 9, 13), dict(tile=0, recompute=False), {"kind": 0, "route": 0}),
     "fused_deferred": ((66, 38, 21), dict(tile=2, pair=0), {"kind": 2, "pairs": 0, "route": 1}),
