@@ -1,7 +1,7 @@
 /*
  * pft_ic_ops.h -- the operators of a compiled `icond` program that the device evaluates bit for bit
  * as the host does (f1, general formulas: pft_ic_compile in pft_frontend.c, ic_prog_kernel in
- * pft_kernels.hip; f12, formula diagnostics: formula_kernel in pft_reduce.hip, which never meets
+ * pft_ic.hip; f12, formula diagnostics: formula_kernel in pft_reduce.hip, which never meets
  * C or P -- pft_formula_compile).  Compiled both as C (the host restatement pft_ic_prog_eval_host that the CPU
  * tests compare with pft_ic_eval) and as HIP device code; always without contraction.
  *

@@ -1,4 +1,5 @@
-// pft_kernels.hip -- hand-written HIP kernels for gfx950 (MI355X) + the pft_hip_* C-ABI shim.
+// pft_kernels.hip -- the hand-written step kernels for gfx950 (MI355X), the slab object's API and
+// the pft_hip_* C-ABI shim.
 //
 // The hot path of RK_MPI_SA_solve (RK_MPI_SAsolver_hybrid2.c:351-766) with the intertrack
 // right-hand side (equation.c:566-884) fused per Merson stage: each stage is ONE kernel that
@@ -19,16 +20,15 @@
 // workgroup id is remapped so that the 8 XCDs each take a contiguous run of tiles (their y
 // neighbours then share the XCD's L2, cdna_hip_programming.md T1).
 //
-// The reductions (pft_reduce.hip) and the snapshots (pft_snap.hip) are translation units of their
-// own over pft_slab.h, which holds the slab object and what the files share.
+// The halo exchange (pft_halo.hip), the device IC (pft_ic.hip), the reductions (pft_reduce.hip) and
+// the snapshots (pft_snap.hip) are translation units of their own over pft_slab.h, which holds the
+// slab object and what the files share.
 #include "pft_slab.h"
 #include "pft_zplan.h"
 static_assert(PFT_K_BOUNDARY == PFT_ZP_BOUNDARY && PFT_K_BOUNDARY2 == PFT_ZP_BOUNDARY2 && PFT_K_INLINE == PFT_ZP_INLINE &&
               PFT_K_ENDS_FIRST == PFT_ZP_ENDS_FIRST, "pft_zplan.h restates the range codes of pft_hip.h");
 
 #include "pft_cosh.h"
-#include "pft_ic_ops.h"
-#include "pft_tanh.h"
 
 #pragma clang fp contract(off)
 
@@ -1925,116 +1925,6 @@ __global__ __launch_bounds__(PFT_PBLOCK) __attribute__((amdgpu_waves_per_eu(2)))
 }
 #pragma clang diagnostic pop
 
-// the copy-engine exchange of an inline boundary (PFT_K_INLINE): this one-wave kernel ends once the
-// boundary workgroups of the launch have counted themselves (*bdone >= target, monotonic), so the
-// plane copies queued behind it on the comm stream start while that launch's interior still runs.
-// It sits on a CU the boundary workgroups freed; nothing it waits for depends on another rank.
-__global__ __launch_bounds__(64) void bnd_trigger_kernel(const unsigned long long* bdone, unsigned long long target)
-{
-  if (threadIdx.x == 0)
-    while (__hip_atomic_load(bdone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(2);
-}
-
-// ------------------------------------------------------------------------------------------
-// f1: the default Params' initial condition and the glass beads on the device (pft_slab_ic_default)
-
-struct IcDev {
-  double* x;             // X
-  double* xn;            // XN (the same values)
-  long fs;
-  int n1, n2, n3, plane;
-  const double* tab;     // tx1 tx2 px2 xb [n1], ty1 ty2 py2 yb [n2], tz1 tz2 pz zb [n3], beads 3*nb
-  const int* poff;       // [n3 + 1]
-  const int* pbead;
-  int nbeads;
-  double u0, r2, s, R, reach2;
-  unsigned int* unclean;
-  int overlay;           // 1: the beads over X's gl (an IC already in X, e.g. ic_prog_kernel's); u, p kept
-};
-
-// one thread per interior node: pft_model_ic_default (Params:9-21 as the reference's evaluator
-// computes them: u = 293.15; p = 1 inside the ice disc, else 0; gl the max of the six wall terms in
-// the formula's order) and overlay_beads (equation.c:507-530: gl = max(gl, 0.5 (1 - tanh(s (|x -
-// b| + 1e-10 - R))))), every operation the host's in the host's order, no contraction
-__global__ __launch_bounds__(256) void ic_default_kernel(IcDev a)
-{
-  const long n = (long)a.plane * a.n3;
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  const int k = (int)(e / a.plane);
-  const int r = (int)(e - (long)k * a.plane);
-  const int j = r / a.n1, i = r - j * a.n1;
-  const double* X = a.tab;
-  const double* Y = X + 4 * a.n1;
-  const double* Z = Y + 4 * a.n2;
-  const double* B = Z + 4 * a.n3;
-  const long o = (long)(k + 1) * a.plane + r;
-  double p = 0.0, gl;
-  if (a.overlay) {
-    gl = a.x[2 * a.fs + o];
-  } else {
-    p = (Z[2 * a.n3 + k] != 0.0 && X[2 * a.n1 + i] + Y[2 * a.n2 + j] < a.r2) ? 1.0 : 0.0;
-    gl = Z[k];
-    gl = gl > Z[a.n3 + k] ? gl : Z[a.n3 + k];           // evmax (ee_wrapper.cc:246-250), in order
-    gl = gl > X[i] ? gl : X[i];
-    gl = gl > Y[j] ? gl : Y[j];
-    gl = gl > X[a.n1 + i] ? gl : X[a.n1 + i];
-    gl = gl > Y[a.n2 + j] ? gl : Y[a.n2 + j];
-  }
-  if (a.nbeads) {
-    const double x = X[3 * a.n1 + i], y = Y[3 * a.n2 + j], z = Z[3 * a.n3 + k];
-    for (int t = a.poff[k]; t < a.poff[k + 1]; ++t) {
-      const int b = a.pbead[t];
-      const double v1 = x - B[3 * b], v2 = y - B[3 * b + 1], v3 = z - B[3 * b + 2];
-      const double d2 = v1 * v1 + v2 * v2 + v3 * v3;
-      if (d2 > a.reach2) continue;
-      const double nrm = sqrt(d2) + 1E-10;
-      const double phf = 0.5 * (1.0 - pft_tanh(a.s * (nrm - a.R)));
-      if (gl < phf) gl = phf;
-    }
-  }
-  if (!a.overlay) {
-    a.x[o] = a.u0;
-    a.x[a.fs + o] = p;
-    a.xn[o] = a.u0;
-    a.xn[a.fs + o] = p;
-  }
-  a.x[2 * a.fs + o] = gl;
-  a.xn[2 * a.fs + o] = gl;
-  if (gl != gl || (gl == 0.0 && signbit(gl))) atomicOr(a.unclean, 1u);
-}
-
-// f1 for any icond formula (pft_ic_compile): one thread per interior node runs the compiled
-// residual program (csrc/pft_ic_ops.h, the host's operators) on the node's u, p, gl in X and the
-// host-evaluated per-axis tables, into field q of X and XN -- as pft_ic_eval does on the host array
-struct IcProgDev {
-  double* x;
-  double* xn;
-  long fs;
-  int n1, n2, n3, plane, q, n;
-  const int* op;
-  const double* arg;
-  const int* taxis;
-  const long* toff;
-  const double* tval;
-  const unsigned char* terr;
-};
-
-__global__ __launch_bounds__(256) void ic_prog_kernel(IcProgDev a)
-{
-  const long n = (long)a.plane * a.n3;
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  const int k = (int)(e / a.plane);
-  const int r = (int)(e - (long)k * a.plane);
-  const int j = r / a.n1, i = r - j * a.n1;
-  const long o = (long)(k + 1) * a.plane + r;
-  const double node[3] = {a.x[o], a.x[a.fs + o], a.x[2 * a.fs + o]};
-  const double v = pft_ic_run(a.n, a.op, a.arg, node, a.taxis, a.toff, a.tval, a.terr, i, j, k);
-  a.x[a.q * a.fs + o] = v;
-  a.xn[a.q * a.fs + o] = v;
-}
-
 // ------------------------------------------------------------------------------------------
 // layout conversion kernels (host padded layout, ghost thickness 2 <-> device layout)
 
@@ -2137,129 +2027,6 @@ __global__ void flat_combine_kernel(int stage, int n_chunks, const int* __restri
       if (bnf) atomicOr(nonfinite, 1u);
     }
   }
-}
-
-// ------------------------------------------------------------------------------------------
-// ipc transport (pft_comm.h): this slab's boundary planes go straight into the z-neighbours' ghost
-// planes (IPC-mapped device memory, on this GPU or over xGMI), then the last workgroup publishes the
-// exchange's sequence number in the neighbours' flag words; each side's stream waits for its own
-// flags (hipStreamWaitValue64), so the next stage starts only once both ghost planes are in.
-
-struct PutArgs {
-  const double* src;          // this slab's buffer (one role)
-  long fs;
-  int plane, n3, f0, nf;
-  double* dlo;                // the neighbour below: its top ghost plane (n3' + 1) of field 0, or null
-  long dlo_fs;
-  double* dhi;                // the neighbour above: its bottom ghost plane (0) of field 0, or null
-  long dhi_fs;
-  int deep;                   // 1: also the second planes, into the neighbours' far ghost planes
-  double* flo;                // the neighbour below's far plane above (n3' + 2) of field 0
-  double* fhi;                // the neighbour above's far plane below (-1) of field 0
-};
-
-__global__ __launch_bounds__(256) void halo_put_kernel(PutArgs a)
-{
-  const long n = (long)a.nf * a.plane;   // doubles per side and depth
-  const long tot = (a.deep ? 4 : 2) * n;
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < tot; e += (long)gridDim.x * blockDim.x) {
-    const int part = (int)(e / n);       // 0: plane 1 down, 1: plane n3 up, 2: plane 2 down (far), 3: plane n3-1 up (far)
-    const long r = e - part * n;
-    const int f = (int)(r / a.plane);
-    const long c = r - (long)f * a.plane;
-    const int q = a.f0 + f;
-    if (part == 0) {
-      if (a.dlo) a.dlo[q * a.dlo_fs + c] = a.src[q * a.fs + (long)a.plane + c];
-    } else if (part == 1) {
-      if (a.dhi) a.dhi[q * a.dhi_fs + c] = a.src[q * a.fs + (long)a.n3 * a.plane + c];
-    } else if (part == 2) {
-      if (a.flo) a.flo[q * a.dlo_fs + c] = a.src[q * a.fs + 2L * a.plane + c];
-    } else {
-      if (a.fhi) a.fhi[q * a.dhi_fs + c] = a.src[q * a.fs + (long)(a.n3 - 1) * a.plane + c];
-    }
-  }
-}
-
-// Staged receive (pft_slab_halo_wait): the planes the neighbours put into this slab's receive
-// buffer rbuf (uncached; two slots by the exchange's parity, each [side][depth][field][plane], side
-// 0 from below, 1 from above; depth 0 the ghost plane, 1 the far ghost plane) copied into the ghost planes of buffer dst, fields
-// [f0, f0 + nf), for the sides in `sides` (bit 0 below, bit 1 above)
-struct RecvArgs {
-  const double* rbuf;
-  double* dst;                // the buffer (pft_slab_buffer layout: plane 0 = ghost below)
-  long fs;
-  int plane, n3, f0, nf, depth, sides;
-};
-
-__global__ __launch_bounds__(256) void halo_recv_kernel(RecvArgs a)
-{
-  const long n = (long)a.nf * a.plane;
-  const long tot = 4L * n;              // (side, depth) parts, skipped where not received
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < tot; e += (long)gridDim.x * blockDim.x) {
-    const int part = (int)(e / n);
-    const int side = part >> 1, depth = part & 1;
-    if (!((a.sides >> side) & 1) || depth >= a.depth) continue;
-    const long r = e - part * n;
-    const int f = (int)(r / a.plane);
-    const long c = r - (long)f * a.plane;
-    const int q = a.f0 + f;
-    const long pl = side == 0 ? (depth == 0 ? 0L : -1L) : (long)a.n3 + 1 + depth;
-    a.dst[q * a.fs + pl * a.plane + c] = a.rbuf[((long)(side * 2 + depth) * 3 + q) * a.plane + c];
-  }
-}
-
-// The receiving side of an exchange in ONE launch (pft_slab_halo_wait): thread 0 of every workgroup
-// waits until both flag words reach seq (system-scope atomic loads of uncached memory: never served
-// from a cache), then -- staged receive -- the workgroups copy the receive buffer into the ghost
-// planes (halo_recv_kernel's loop).  It replaces hipStreamWaitValue64 per flag (the runtime runs each
-// as a kernel of its own, ~3 us apiece) and the separate receive launch.  Every wave exits: the
-// flags come from the neighbours, or from the slab itself when a wait times out (slab_timed_out
-// releases them past every sequence number).
-struct WaitArgs {
-  const unsigned long long* f0;   // flag from below, or null
-  const unsigned long long* f1;   // flag from above, or null
-  unsigned long long seq;
-  int recv;                       // 1: then copy r
-  RecvArgs r;
-};
-
-__global__ __launch_bounds__(256) void halo_wait_kernel(WaitArgs a)
-{
-  if (threadIdx.x == 0) {
-    if (a.f0)
-      while (__hip_atomic_load(a.f0, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < a.seq) __builtin_amdgcn_s_sleep(2);
-    if (a.f1)
-      while (__hip_atomic_load(a.f1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < a.seq) __builtin_amdgcn_s_sleep(2);
-  }
-  __syncthreads();
-  if (!a.recv) return;
-  const RecvArgs& r = a.r;
-  const long n = (long)r.nf * r.plane;
-  const long tot = 4L * n;
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < tot; e += (long)gridDim.x * blockDim.x) {
-    const int part = (int)(e / n);
-    const int side = part >> 1, depth = part & 1;
-    if (!((r.sides >> side) & 1) || depth >= r.depth) continue;
-    const long rr = e - part * n;
-    const int f = (int)(rr / r.plane);
-    const long c = rr - (long)f * r.plane;
-    const int q = r.f0 + f;
-    const long pl = side == 0 ? (depth == 0 ? 0L : -1L) : (long)r.n3 + 1 + depth;
-    r.dst[q * r.fs + pl * r.plane + c] = r.rbuf[((long)(side * 2 + depth) * 3 + q) * r.plane + c];
-  }
-}
-
-// raises the neighbours' flags once the kernels before it on the stream (the put, or a stage
-// kernel that stored its boundary planes into the neighbours' ghost planes) have completed: their
-// stores are released at kernel end; with a neighbour on another GPU a system-scope fence first
-// (the flag must not overtake the plane over xGMI).  One thread, vector atomics only.
-__global__ void halo_signal_kernel(unsigned long long* slo, unsigned long long* shi, unsigned long long seq,
-                                   int remote)
-{
-  if (threadIdx.x != 0) return;
-  if (remote) __threadfence_system();
-  if (slo) __hip_atomic_store(slo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (shi) __hip_atomic_store(shi, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2788,7 +2555,7 @@ static int launch_planned(pft_slab* s, const pft_zplan& p, bool beside, F&& laun
     // at 256 VGPRs leaves no room beside its workgroups: a trigger queued later waited for a CU
     // until this launch drained -- the copies then ran after it)
     if (s->trig_early) {
-      bnd_trigger_kernel<<<1, 64, 0, s->comm>>>(s->bdone, s->bdone_target);
+      slab_trigger(s);
       HIPCHK(hipGetLastError());
     }
   }
@@ -3205,144 +2972,6 @@ int pft_slab_set_noise(pft_slab* s, const double* host_noise)
   const size_t bytes = sizeof(double) * (size_t)s->plane * s->d.n3;
   if (!s->noise) HIPCHK(hipMalloc((void**)&s->noise, bytes));
   HIPCHK(hipMemcpy(s->noise, host_noise, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-
-static int slab_ic_tables(pft_slab* s, const pft_ic_tables* t, int overlay, int* gl_unclean)
-{
-  if (!t || t->n1 != s->d.n1 || t->n2 != s->d.n2 || t->n3 != s->d.n3) return -2;
-  const int n1 = t->n1, n2 = t->n2, n3 = t->n3, nb = t->nbeads;
-  const long nbi = nb ? t->plane_off[n3] : 0;
-  const size_t nd = 4 * (size_t)(n1 + n2 + n3) + 3 * (size_t)nb;
-  const size_t ni = (size_t)(n3 + 1) + (size_t)nbi;
-  std::vector<double> hd(nd);
-  std::vector<int> hi(ni, 0);
-  const double* src[12] = {t->tx1, t->tx2, t->px2, t->xb, t->ty1, t->ty2, t->py2, t->yb,
-                           t->tz1, t->tz2, t->pz, t->zb};
-  const int len[3] = {n1, n2, n3};
-  size_t o = 0;
-  for (int a = 0; a < 3; ++a)
-    for (int q = 0; q < 4; ++q) {
-      memcpy(&hd[o], src[4 * a + q], sizeof(double) * len[a]);
-      o += len[a];
-    }
-  if (nb) {
-    memcpy(&hd[o], t->bxyz, sizeof(double) * 3 * nb);
-    memcpy(&hi[0], t->plane_off, sizeof(int) * (n3 + 1));
-    if (nbi) memcpy(&hi[n3 + 1], t->plane_beads, sizeof(int) * nbi);
-  }
-  double* dd = nullptr;
-  int* di = nullptr;
-  unsigned int* du = nullptr;
-  IcDev a;
-  memset(&a, 0, sizeof(a));
-  hipError_t e = hipMalloc((void**)&dd, sizeof(double) * nd);
-  if (e == hipSuccess) e = hipMalloc((void**)&di, sizeof(int) * ni);
-  if (e == hipSuccess) e = hipMalloc((void**)&du, sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMemcpyAsync(dd, hd.data(), sizeof(double) * nd, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(di, hi.data(), sizeof(int) * ni, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(du, 0, sizeof(unsigned int), s->stream);
-  if (e == hipSuccess) {
-    a.x = s->buf[PFT_BUF_X];
-    a.xn = s->buf[PFT_BUF_XN];
-    a.fs = s->fs;
-    a.n1 = n1;
-    a.n2 = n2;
-    a.n3 = n3;
-    a.plane = s->plane;
-    a.tab = dd;
-    a.poff = di;
-    a.pbead = di + n3 + 1;
-    a.nbeads = nb;
-    a.u0 = t->u0;
-    a.r2 = t->r2;
-    a.s = t->s;
-    a.R = t->R;
-    a.reach2 = t->reach2;
-    a.unclean = du;
-    a.overlay = overlay;
-    const long n = (long)s->plane * n3;
-    ic_default_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s->stream>>>(a);
-    e = hipGetLastError();
-  }
-  unsigned int hu = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&hu, du, sizeof(unsigned int), hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  (void)hipFree(dd);
-  (void)hipFree(di);
-  (void)hipFree(du);
-  if (e != hipSuccess) return fail(e, "pft_slab_ic_default");
-  if (gl_unclean) *gl_unclean = hu ? 1 : 0;
-  return 0;
-}
-
-int pft_slab_ic_default(pft_slab* s, const pft_ic_tables* t, int* gl_unclean)
-{
-  return slab_ic_tables(s, t, 0, gl_unclean);
-}
-
-int pft_slab_ic_beads(pft_slab* s, const pft_ic_tables* t, int* gl_unclean)
-{
-  return slab_ic_tables(s, t, 1, gl_unclean);
-}
-
-int pft_slab_ic_program(pft_slab* s, int q, const pft_ic_prog* p, int clear)
-{
-  if (!p || q < 0 || q > 2 || p->n < 1) return -2;
-  hipError_t e = hipSuccess;
-  if (clear) {
-    // the host array the reference's loop fills starts zeroed: quantities not yet initialised read 0
-    e = hipMemsetAsync(s->buf[PFT_BUF_X], 0, sizeof(double) * 3 * (size_t)s->fs, s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->buf[PFT_BUF_XN], 0, sizeof(double) * 3 * (size_t)s->fs, s->stream);
-  }
-  const size_t nt = (size_t)(p->ntab > 0 ? p->ntab : 1), nv = (size_t)(p->tab_len > 0 ? p->tab_len : 1);
-  const size_t bytes = sizeof(int) * p->n + sizeof(double) * p->n + sizeof(int) * nt + sizeof(long) * nt +
-                       sizeof(double) * nv + nv + 64;
-  std::vector<char> h(bytes, 0);
-  // one upload: [arg (n doubles)][tval (nv doubles)][toff (nt longs)][op (n ints)][taxis (nt ints)][terr]
-  size_t o = 0;
-  const size_t o_arg = o;  o += sizeof(double) * p->n;
-  const size_t o_val = o;  o += sizeof(double) * nv;
-  const size_t o_off = o;  o += sizeof(long) * nt;
-  const size_t o_op = o;   o += sizeof(int) * p->n;
-  const size_t o_ax = o;   o += sizeof(int) * nt;
-  const size_t o_err = o;
-  memcpy(&h[o_arg], p->arg, sizeof(double) * p->n);
-  memcpy(&h[o_op], p->op, sizeof(int) * p->n);
-  if (p->ntab > 0) {
-    memcpy(&h[o_val], p->tab_val, sizeof(double) * p->tab_len);
-    memcpy(&h[o_off], p->tab_off, sizeof(long) * p->ntab);
-    memcpy(&h[o_ax], p->tab_axis, sizeof(int) * p->ntab);
-    memcpy(&h[o_err], p->tab_err, p->tab_len);
-  }
-  char* d = nullptr;
-  if (e == hipSuccess) e = hipMalloc((void**)&d, bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess) {
-    IcProgDev a;
-    a.x = s->buf[PFT_BUF_X];
-    a.xn = s->buf[PFT_BUF_XN];
-    a.fs = s->fs;
-    a.n1 = s->d.n1;
-    a.n2 = s->d.n2;
-    a.n3 = s->d.n3;
-    a.plane = s->plane;
-    a.q = q;
-    a.n = p->n;
-    a.arg = (const double*)(d + o_arg);
-    a.tval = (const double*)(d + o_val);
-    a.toff = (const long*)(d + o_off);
-    a.op = (const int*)(d + o_op);
-    a.taxis = (const int*)(d + o_ax);
-    a.terr = (const unsigned char*)(d + o_err);
-    const long n = (long)s->plane * s->d.n3;
-    ic_prog_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s->stream>>>(a);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  if (d) (void)hipFree(d);
-  if (e != hipSuccess) return fail(e, "pft_slab_ic_program");
-  s->gl_keep = 0;
   return 0;
 }
 
@@ -3892,504 +3521,6 @@ int pft_slab_swap_buffers(pft_slab* s, int a, int b)
 }
 
 int pft_slab_accept(pft_slab* s) { return pft_slab_swap_buffers(s, PFT_BUF_X, PFT_BUF_XN); }
-
-static int ensure_rbuf(pft_slab* s)
-{
-  // two slots (exchange sequence number parity): a neighbour can be one exchange ahead -- its
-  // next put needs only our flag of this exchange, which we raise before copying its planes out
-  if (!s->rbuf) HIPCHK(hipExtMallocWithFlags((void**)&s->rbuf, sizeof(double) * 24 * (size_t)s->plane, hipDeviceMallocUncached));
-  return 0;
-}
-
-int pft_slab_ipc_export(pft_slab* s, void* handles)
-{
-  hipIpcMemHandle_t* h = (hipIpcMemHandle_t*)handles;
-  int rc = ensure_rbuf(s);
-  if (rc) return rc;
-  for (int b = 0; b < PFT_BUF_COUNT; ++b) HIPCHK(hipIpcGetMemHandle(&h[b], s->buf0[b]));
-  HIPCHK(hipIpcGetMemHandle(&h[PFT_BUF_COUNT], s->sig));
-  HIPCHK(hipIpcGetMemHandle(&h[PFT_BUF_COUNT + 1], s->rbuf));
-  return 0;
-}
-
-int pft_ipc_staged_env(void)
-{
-  const char* e = getenv("PFT_IPC_STAGED");
-  return e && atoi(e) == 1;
-}
-
-int pft_slab_ipc_set_peer(pft_slab* s, int side, const void* handles, int n3, long fs, int remote,
-                          int peer_staged)
-{
-  if (side < 0 || side > 1) return -2;
-  SlabPeer& p = s->peer[side];
-  if (p.on) return -2;                  // pft_slab_ipc_close first
-  if (!handles) {
-    // self exchange (diagnostic, one slab): the planes land in the slab's own ghost planes, which a
-    // single slab never reads (mirror bottom, Dirichlet top)
-    int rc = ensure_rbuf(s);
-    if (rc) return rc;
-    for (int b = 0; b < PFT_BUF_COUNT; ++b) p.base[b] = s->buf0[b] + s->plane;
-    p.sig = s->sig;
-    p.rbuf = s->rbuf;
-    p.staged = pft_ipc_staged_env();
-    p.n3 = s->d.n3;
-    p.fs = s->fs;
-    p.opened = 0;
-    p.on = 1;
-    return 0;
-  }
-  const hipIpcMemHandle_t* h = (const hipIpcMemHandle_t*)handles;
-  for (int b = 0; b <= PFT_BUF_COUNT + 1; ++b) {
-    void* ptr = nullptr;
-    const hipError_t e = hipIpcOpenMemHandle(&ptr, h[b], hipIpcMemLazyEnablePeerAccess);
-    if (e != hipSuccess) {
-      for (int q = 0; q < b && q < PFT_BUF_COUNT; ++q) (void)hipIpcCloseMemHandle(p.base[q] - s->plane);
-      if (b > PFT_BUF_COUNT) (void)hipIpcCloseMemHandle(p.sig);
-      return fail(e, "hipIpcOpenMemHandle");
-    }
-    if (b < PFT_BUF_COUNT) p.base[b] = (double*)ptr + s->plane;   // the neighbour's buffer pointer
-    else if (b == PFT_BUF_COUNT) p.sig = (unsigned long long*)ptr;
-    else p.rbuf = (double*)ptr;
-  }
-  p.n3 = n3;
-  p.fs = fs;
-  p.remote = remote ? 1 : 0;   // the caller compared the GPUs' identities (pft_hip_device_ident)
-  // A neighbour on another GPU writes into our receive buffer (uncached) rather than our ghost
-  // planes, and we copy it in after the flag wait: no L2 of ours can hold a stale line of what it
-  // wrote.  Both sides take the same decision: remote is symmetric, and the
-  // env (the test hook that stages between processes on one GPU) counts if either side set it --
-  // a sender putting into ghost planes that the receiver overwrites from its receive buffer, or
-  // the other way round, would corrupt the halo without any error.
-  p.staged = p.remote || pft_ipc_staged_env() || peer_staged;
-  p.opened = 1;
-  p.on = 1;
-  return 0;
-}
-
-int pft_slab_ipc_close(pft_slab* s)
-{
-  if (s->ipc_poisoned == 1) {
-    // the flags were forced past every sequence number: back to 0 for the next attach (the compute
-    // stream has drained, slab_wait)
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipStreamSynchronize(s->side);
-    if (s->bnd) (void)hipStreamSynchronize(s->bnd);
-
-    (void)hipStreamSynchronize(s->comm);
-    HIPCHK(hipMemset(s->sig, 0, 2 * sizeof(unsigned long long)));
-    HIPCHK(hipDeviceSynchronize());
-    s->ipc_poisoned = 0;
-  }
-  if ((s->peer[0].on && s->peer[0].opened) || (s->peer[1].on && s->peer[1].opened)) {
-    // the copy-engine exchange's streams write into the mappings about to be closed: drained first
-    // (they wait only on compute-stream work, which the detach's pft_slab_sync has drained)
-    if (s->comm) (void)hipStreamSynchronize(s->comm);
-    if (s->side) (void)hipStreamSynchronize(s->side);
-  }
-  for (int side = 0; side < 2; ++side) {
-    SlabPeer& p = s->peer[side];
-    if (p.on && p.opened) {
-      for (int b = 0; b < PFT_BUF_COUNT; ++b) (void)hipIpcCloseMemHandle(p.base[b] - s->plane);
-      (void)hipIpcCloseMemHandle(p.sig);
-      (void)hipIpcCloseMemHandle(p.rbuf);
-    }
-    memset(&p, 0, sizeof(p));
-  }
-  return 0;
-}
-
-int pft_slab_halo_put(pft_slab* s, int role, int f0, int f1, unsigned long long seq)
-{
-  return pft_slab_halo_put2(s, role, f0, f1, 0, seq);
-}
-
-double* pft_slab_far(pft_slab* s, int which, int q, int side)
-{
-  if (which < 0 || which >= PFT_BUF_COUNT || q < 0 || q > 2 || side < 0 || side > 1) return nullptr;
-  return s->buf[which] + q * s->fs + (side ? (long)(s->d.n3 + 2) * s->plane : -(long)s->plane);
-}
-
-int pft_slab_halo_put2(pft_slab* s, int role, int f0, int f1, int deep, unsigned long long seq)
-{
-  if (role < 0 || role >= PFT_BUF_COUNT || f0 < 0 || f1 > 3 || f1 <= f0) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_halo_put2");
-  s->put_role = role;
-  s->put_f0 = f0;
-  s->put_f1 = f1;
-  s->put_deep = deep ? 1 : 0;
-  if (s->drop_puts) return 0;
-  const int ph = s->phys[role];
-  PutArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src = s->buf[role];
-  a.fs = s->fs;
-  a.plane = s->plane;
-  a.n3 = s->d.n3;
-  a.f0 = f0;
-  a.nf = f1 - f0;
-  // staged: into the neighbour's receive buffer [side][depth][field][plane] -- the neighbour below
-  // receives our planes as "from above" (side 1), the one above as "from below" (side 0)
-  const long P = s->plane;
-  const long slot = (long)(seq & 1) * 12 * P;   // the receive-buffer slot of this exchange
-  if (s->peer[0].on) {
-    a.dlo = s->peer[0].staged ? s->peer[0].rbuf + slot + (1 * 2 + 0) * 3 * P : s->peer[0].base[ph] + (long)(s->peer[0].n3 + 1) * P;
-    a.dlo_fs = s->peer[0].staged ? P : s->peer[0].fs;
-  }
-  if (s->peer[1].on) {
-    a.dhi = s->peer[1].staged ? s->peer[1].rbuf + slot + (0 * 2 + 0) * 3 * P : s->peer[1].base[ph];
-    a.dhi_fs = s->peer[1].staged ? P : s->peer[1].fs;
-  }
-  if (!a.dlo && !a.dhi) return 0;
-  if (deep) {
-    // the second boundary planes into the neighbours' far ghost planes (pft_slab_far layout)
-    a.deep = 1;
-    if (s->peer[0].on)
-      a.flo = s->peer[0].staged ? s->peer[0].rbuf + slot + (1 * 2 + 1) * 3 * P : s->peer[0].base[ph] + (long)(s->peer[0].n3 + 2) * P;
-    if (s->peer[1].on) a.fhi = s->peer[1].staged ? s->peer[1].rbuf + slot + (0 * 2 + 1) * 3 * P : s->peer[1].base[ph] - P;
-  }
-  const long n = (deep ? 4L : 2L) * a.nf * s->plane;
-  const int blocks = (int)std::min<long>(1024, std::max<long>(1, (n + 255) / 256));
-  halo_put_kernel<<<blocks, 256, 0, s->stream>>>(a);
-  HIPCHK(hipGetLastError());
-  return pft_slab_halo_signal(s, seq);
-}
-
-#define PFT_SEQTAB 4096
-
-// The ipc exchange on the copy engines (SDMA): after the launch that wrote the boundary planes (an
-// event on the compute stream), the comm stream copies them into the neighbours' ghost (and far
-// ghost) planes -- or their receive buffers when staged -- with hipMemcpyDeviceToDeviceNoCU, then
-// raises the neighbours' flags with 8-byte copies of the sequence number from seqtab.  No kernel:
-// the copies need no CU, so they run beside the interior launch that holds every CU's LDS (a blit
-// kernel, or RCCL's, waits for that launch to end: profiles/r05_sdma_probe.txt).  The receiver
-// side is unchanged (pft_slab_halo_wait: the compute stream waits for the flags; staged: the
-// receive kernel), so a sender may use either put.
-int pft_slab_halo_put_ce(pft_slab* s, int role, int f0, int f1, int deep, unsigned long long seq)
-{
-  if (role < 0 || role >= PFT_BUF_COUNT || f0 < 0 || f1 > 3 || f1 <= f0 || seq == 0) return -2;
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_halo_put_ce");
-  const int marked = s->ce_marked;
-  s->ce_marked = 0;
-  s->put_role = role;
-  s->put_f0 = f0;
-  s->put_f1 = f1;
-  s->put_deep = deep ? 1 : 0;
-  if (s->drop_puts) return 0;
-  if (!s->peer[0].on && !s->peer[1].on) return 0;
-  if (!s->seqtab) {
-    HIPCHK(hipMalloc((void**)&s->seqtab, sizeof(unsigned long long) * PFT_SEQTAB));
-    HIPCHK(hipHostMalloc((void**)&s->seqhost, 2 * sizeof(unsigned long long) * PFT_SEQTAB, hipHostMallocDefault));
-    for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&s->ev_seq[i], hipEventDisableTiming));
-    s->seq_base = ~0ULL;
-    // test hook PFT_CE_SEQTAB=n (2..4096): a table of n numbers, refilled every n exchanges
-    const char* et = getenv("PFT_CE_SEQTAB");
-    s->seq_n = (et && atoi(et) >= 2 && atoi(et) <= PFT_SEQTAB) ? atoi(et) : PFT_SEQTAB;
-    // the flags behind an explicit completion of the plane copies (default 1; PFT_CE_FENCE=0: each
-    // flag copy right behind its planes on the same stream, relying on the in-order SDMA queue)
-    const char* ef = getenv("PFT_CE_FENCE");
-    s->ce_fence = !(ef && atoi(ef) == 0);
-    for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&s->ev_planes[i], hipEventDisableTiming));
-  }
-  const int NSEQ = s->seq_n;
-  if (s->seq_base == ~0ULL || seq <= s->seq_base || seq > s->seq_base + NSEQ) {
-    // the next block of sequence numbers, from the pinned half not used by the previous refill
-    s->seq_base = (seq - 1) / NSEQ * NSEQ;
-    s->seq_half ^= 1;
-    if (s->ce_streams != 1) {
-      // the side stream's last flag copy reads the old table: the refill (comm stream) waits for it
-      HIPCHK(hipEventRecord(s->ev_side, s->side));
-      HIPCHK(hipStreamWaitEvent(s->comm, s->ev_side, 0));
-    }
-    // this pinned half was last read by the refill copy two refills ago: the host rewrites it only
-    // once that copy has run (with a small table -- the PFT_CE_SEQTAB test hook -- the speculative
-    // pipeline can hold that many exchanges queued)
-    // (bounded like every host wait with ipc peers: a lost peer can hold that copy's stream)
-    {
-      const int wrc = slab_wait(s, s->ev_seq[s->seq_half], "pft_slab_halo_put_ce (seqtab refill)");
-      if (wrc) return wrc;
-    }
-    unsigned long long* h = s->seqhost + (size_t)s->seq_half * PFT_SEQTAB;
-    for (int i = 0; i < NSEQ; ++i) h[i] = s->seq_base + 1 + i;
-    HIPCHK(hipMemcpyAsync(s->seqtab, h, sizeof(unsigned long long) * NSEQ, hipMemcpyHostToDevice, s->comm));
-    HIPCHK(hipEventRecord(s->ev_seq[s->seq_half], s->comm));
-    if (s->ce_streams != 1) {
-      // the side stream's flag copies read the new table: this exchange's (and so every later one's)
-      // follow the refill.  (An event on every exchange instead held each side flag behind the comm
-      // stream's copies and put a marker between the comm stream's last copy and its flag: ~10-20
-      // us later flags, profiles/r05_ce_trace_pipe.txt.)
-      HIPCHK(hipEventRecord(s->ev_copy, s->comm));
-      HIPCHK(hipStreamWaitEvent(s->side, s->ev_copy, 0));
-    }
-  }
-  // the planes to the neighbour below go on the comm stream, to the one above on the side stream
-  // (two copy engines; ce_streams = 1: all on the comm stream), each followed by its neighbour's
-  // flag.  (Four streams, a side's copies alternating between two, measured slower: 11 300-12 600
-  // against 16 000 Mcells*steps/s on the 800^3 rank slab, profiles/r05_ce_ab.txt; removed.)
-  hipStream_t cs[2] = {s->comm, s->ce_streams == 1 ? s->comm : s->side};
-  if (s->inline_pending) {
-    // inline boundary: the copies start once the launch's boundary workgroups have counted
-    // themselves -- not at its end, and with no event on the compute stream between them
-    // (trig_early: the trigger is on the comm stream already, queued with the launch)
-    s->inline_pending = 0;
-    if (!s->trig_early) {
-      bnd_trigger_kernel<<<1, 64, 0, cs[0]>>>(s->bdone, s->bdone_target);
-      HIPCHK(hipGetLastError());
-    }
-    if (cs[1] != cs[0]) {
-      HIPCHK(hipEventRecord(s->ev_trig, cs[0]));
-      HIPCHK(hipStreamWaitEvent(cs[1], s->ev_trig, 0));
-    }
-  } else {
-    hipEvent_t ready = s->bnd_pending ? s->ev_bnd : s->ev_order[0];
-    if (!s->bnd_pending && !marked) HIPCHK(hipEventRecord(s->ev_order[0], s->stream));
-    HIPCHK(hipStreamWaitEvent(cs[0], ready, 0));
-    if (cs[1] != cs[0]) HIPCHK(hipStreamWaitEvent(cs[1], ready, 0));
-  }
-  const int ph = s->phys[role];
-  const long P = s->plane, n3 = s->d.n3;
-  const long slot = (long)(seq & 1) * 12 * P;
-  const size_t pb = sizeof(double) * (size_t)P;
-  for (int side = 0; side < 2; ++side) {
-    const SlabPeer& p = s->peer[side];
-    if (!p.on) continue;
-    for (int q = f0; q < f1; ++q) {
-      const double* src = s->buf[role] + q * s->fs;
-      if (!p.staged) {
-        // below: our planes 1 (, 2) into its ghost n3'+1 (, far n3'+2); above: our planes (n3-1,) n3
-        // into its (far -1,) ghost 0 -- contiguous on both ends
-        double* dst = side == 0 ? p.base[ph] + q * p.fs + (p.n3 + 1) * P : p.base[ph] + q * p.fs - (deep ? P : 0);
-        const double* sp = side == 0 ? src + P : src + (deep ? n3 - 1 : n3) * P;
-        HIPCHK(hipMemcpyAsync(dst, sp, (deep ? 2 : 1) * pb, hipMemcpyDeviceToDeviceNoCU, cs[side]));
-      } else {
-        // its receive buffer [slot][side][depth][field][plane]: the neighbour below receives our
-        // planes as "from above" (side 1), the one above as "from below" (side 0)
-        for (int d = 0; d < (deep ? 2 : 1); ++d) {
-          double* dst = p.rbuf + slot + ((long)((side == 0 ? 1 : 0) * 2 + d) * 3 + q) * P;
-          const double* sp = side == 0 ? src + (1 + d) * P : src + (n3 - d) * P;
-          HIPCHK(hipMemcpyAsync(dst, sp, pb, hipMemcpyDeviceToDeviceNoCU, cs[side]));
-        }
-      }
-    }
-  }
-  const unsigned long long* sv = s->seqtab + (seq - 1 - s->seq_base);
-  // The neighbour reads the planes once it sees the flag, so the flag must not land before them.
-  // ce_fence (default): the flag copy goes on a stream of its own behind an event recorded after
-  // the side's plane copies.  The runtime turns that event wait into a dependency on the copies'
-  // completion signal (hsa_amd_memory_async_copy, hsa_ext_amd.h: "the copy will start after every
-  // [dependent] signal has been observed with the value 0", and the completion signal is
-  // decremented "when the copy operation is finished"), so the flag copy starts only after the
-  // plane copies have finished -- an ordering the HSA interface states, where a flag copy right
-  // behind them on the same stream relies on the SDMA queue retiring its writes in order (not a
-  // documented property across xGMI; PFT_CE_FENCE=0 restores that form for A/B).  The receiver's
-  // side is the system-scope acquire load of the flag in halo_wait_kernel (hsa_ext_amd.h asks the
-  // receiving device for a system-scope acquire before it uses a copy's destination).
-  // No stream is added for it: a process has 4 hardware queues (GPU_MAX_HW_QUEUES) and already 4
-  // streams (compute, boundary, comm, side); a fifth and sixth share queues with them, and their
-  // waits then hold up unrelated work -- one flag stream per side measured that way (DESIGN
-  // section 6).  So each side's flag goes on the OTHER copy stream, behind an event after this
-  // side's planes: with two neighbours both flags land after both sides' planes (the two run side
-  // by side, of equal size), each ordered after its own planes by the event.  With one copy stream
-  // (ce_streams 1) the stream order is all there is.
-  hipStream_t fs[2] = {cs[0], cs[1]};
-  if (s->ce_fence && cs[1] != cs[0]) {
-    for (int side = 0; side < 2; ++side)
-      if (s->peer[side].on) HIPCHK(hipEventRecord(s->ev_planes[side], cs[side]));
-    for (int side = 0; side < 2; ++side)
-      if (s->peer[side].on) {
-        fs[side] = cs[1 - side];
-        HIPCHK(hipStreamWaitEvent(fs[side], s->ev_planes[side], 0));
-      }
-  }
-  if (s->peer[0].on) HIPCHK(hipMemcpyAsync(s->peer[0].sig + 1, sv, 8, hipMemcpyDeviceToDeviceNoCU, fs[0]));
-  if (s->peer[1].on) HIPCHK(hipMemcpyAsync(s->peer[1].sig + 0, sv, 8, hipMemcpyDeviceToDeviceNoCU, fs[1]));
-  return 0;
-}
-
-int pft_slab_halo_mark(pft_slab* s)
-{
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_halo_mark");
-  if (!s->bnd_pending && !s->inline_pending) HIPCHK(hipEventRecord(s->ev_order[0], s->stream));
-  s->ce_marked = 1;
-  return 0;
-}
-
-int pft_slab_set_boundary_stream(pft_slab* s, int on)
-{
-  if (on && !s->bnd) {
-    int lo = 0, hi = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIPCHK(hipStreamCreateWithPriority(&s->bnd, hipStreamNonBlocking, hi));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_bnd, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_pre, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_copy, hipEventDisableTiming));
-  }
-  if (on && !s->ev_copy) HIPCHK(hipEventCreateWithFlags(&s->ev_copy, hipEventDisableTiming));
-  // bnd_mode 2: the pair kernels' boundary launch on its own stream beside their interior launch
-  // (run_pair); a stage launch's boundary runs before its interior.  3 (round 5's default): the
-  // boundary pipeline -- as 2, and the halo waits on the boundary stream (pft_slab_halo_wait), so
-  // that no pair interior launch waits for a neighbour's flag (profiles/r05_ce_shapes.txt: +1% over 2
-  // on one GPU).  5 (default since round 6): one pair launch per exchange, no boundary launch --
-  // pair 2+3 with every tile column's first and last z-chunk leading the grid (PFT_K_ENDS_FIRST),
-  // pair 4+5 with two-plane boundary chunks leading its interior chunks (PFT_K_INLINE, see
-  // pft_slab_pair_inline); the copies start behind bnd_trigger_kernel once those workgroups are
-  // done, while the rest of the launch runs.  The interior launch of 2 / 3 holds the CUs for
-  // several rounds of workgroups on the driver's N > 1 slabs, so their boundary launch beside it
-  // ran late and its copies after it (profiles/r06_ce_shapes.txt).  4: placement 4 for both pairs.
-  // Stage launches keep their boundary first (inline with PFT_CE_STAGE_INLINE=1: slower, the
-  // boundary workgroups' write-backs in a 3-workgroups-per-CU launch).  Env overrides for A/B
-  // (profiles/r05_ce_ab.txt, r05_ce_shapes.txt, r06_ce_shapes.txt): PFT_CE_BND=2 the
-  // waits on the compute stream, 0 every boundary before its interior, 1 every one beside (slower:
-  // a stage launch's interior fills the chip, the two launches' workgroups are dealt interleaved
-  // and the boundary ends late, profiles/r05_ce_trace_bnd.txt); PFT_CE_STREAMS=1 puts every copy
-  // on the comm stream (slower)
-  const char* eb = getenv("PFT_CE_BND");
-  const char* es = getenv("PFT_CE_STREAMS");
-  s->bnd_mode = !on ? 0 : eb && atoi(eb) >= 0 && atoi(eb) <= 5 ? atoi(eb) : 5;
-  if (s->bnd_mode >= 4 && !s->bdone) {
-    HIPCHK(hipMalloc((void**)&s->bdone, 64));
-    HIPCHK(hipMemsetAsync(s->bdone, 0, 64, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->bdone_target = 0;
-    HIPCHK(hipEventCreateWithFlags(&s->ev_trig, hipEventDisableTiming));
-  }
-  s->inline_pending = 0;
-  {
-    const char* et = getenv("PFT_CE_TRIG");
-    const char* esi = getenv("PFT_CE_STAGE_INLINE");
-    s->trig_early = et ? atoi(et) != 0 : 1;
-    s->stage_inline = esi ? atoi(esi) != 0 : 0;
-  }
-  {
-    // CUs reserved for the boundary launches (PFT_CE_RESERVE=R): the compute stream is re-created
-    // with a CU mask that leaves R CUs out, so an interior launch of several rounds of workgroups
-    // can never hold the CUs the boundary launch beside it needs.  R/8 per XCD, chosen so that
-    // either numbering of the mask (CU-major per XCD or XCD-interleaved) spreads them evenly.
-    const char* er = getenv("PFT_CE_RESERVE");
-    const int want = on && s->bnd_mode >= 2 && er ? atoi(er) : 0;
-    if (want != s->cu_reserved && want >= 0 && want <= 32 && want % 8 == 0 && s->n_cu == 256) {
-      uint32_t mask[8];
-      for (int w = 0; w < 8; ++w) mask[w] = ~0u;
-      for (int x = 0; x < 8; ++x)
-        for (int j = 0; j < want / 8; ++j) {
-          const int bit = 32 * x + 8 * j + x;   // residue x mod 8, in the block of 32 numbered x
-          mask[bit / 32] &= ~(1u << (bit % 32));
-        }
-      hipStream_t ns = nullptr;
-      HIPCHK(hipStreamSynchronize(s->stream));
-      HIPCHK(hipExtStreamCreateWithCUMask(&ns, 8, mask));
-      HIPCHK(hipStreamDestroy(s->stream));
-      s->stream = ns;
-      s->cu_reserved = want;
-    }
-  }
-  s->ce_streams = es && atoi(es) == 1 ? 1 : 2;
-  if (s->ce_streams == 2 && !s->ev_copy) HIPCHK(hipEventCreateWithFlags(&s->ev_copy, hipEventDisableTiming));
-  if (!s->ev_side) HIPCHK(hipEventCreateWithFlags(&s->ev_side, hipEventDisableTiming));
-  if (!s->ev_join) HIPCHK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-  s->bnd_pending = 0;
-  return 0;
-}
-
-int pft_slab_halo_signal(pft_slab* s, unsigned long long seq)
-{
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_halo_signal");
-  if (s->drop_puts) return 0;
-  unsigned long long* slo = s->peer[0].on ? s->peer[0].sig + 1 : nullptr;   // below: its "from above"
-  unsigned long long* shi = s->peer[1].on ? s->peer[1].sig + 0 : nullptr;   // above: its "from below"
-  if (!slo && !shi) return 0;
-  halo_signal_kernel<<<1, 64, 0, s->stream>>>(slo, shi, seq,
-                                              s->peer[0].remote || s->peer[1].remote || s->peer[0].staged || s->peer[1].staged);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int pft_slab_halo_wait(pft_slab* s, unsigned long long seq)
-{
-  // flags [0] (from below) and [1] (from above): the stream goes on once both planes are in
-  if (s->ipc_poisoned) return slab_poisoned(s, "pft_slab_halo_wait");
-  // the boundary pipeline (bnd_mode 3): after a boundary launch beside the interior, the flags are
-  // waited for on the boundary stream -- only the next boundary launch (after this wait on that
-  // stream) reads ghost planes; the next interior launch waits for this boundary launch alone
-  hipStream_t ws = s->stream;
-  if (s->bnd_pending) {
-    // the boundary launch ran beside the interior one: its planes are the next launch's input
-    HIPCHK(hipStreamWaitEvent(s->stream, s->ev_bnd, 0));
-    s->bnd_pending = 0;
-    if (s->bnd_mode == 3) ws = s->bnd;
-  } else if (s->bnd_split && s->bnd_mode == 3 && s->bnd) {
-    // a boundary launch before its interior (stage 1): its flags too are waited for on the
-    // boundary stream, which the next boundary launch follows (run_pair beside, run_stage joins)
-    ws = s->bnd;
-  }
-  s->bnd_split = 0;
-  int sides = 0;
-  WaitArgs w;
-  memset(&w, 0, sizeof(w));
-  w.seq = seq;
-  for (int side = 0; side < 2; ++side) {
-    if (!s->peer[side].on) continue;
-    (side == 0 ? w.f0 : w.f1) = s->sig + side;
-    if (s->peer[side].staged) sides |= 1 << side;
-  }
-  if (!w.f0 && !w.f1) return 0;
-  int local_staged = 0;
-  for (int side = 0; side < 2; ++side)
-    if (((sides >> side) & 1) && !s->peer[side].remote) local_staged = 1;
-  int blocks = 1;
-  if (sides) {
-    // staged: what the neighbours put into the receive buffer, into the ghost planes of the
-    // exchange's buffer (the one the last halo_put2 sent: every rank runs the same sequence)
-    RecvArgs& r = w.r;
-    r.rbuf = s->rbuf + (long)(seq & 1) * 12 * s->plane;
-    r.dst = s->buf[s->put_role];
-    r.fs = s->fs;
-    r.plane = s->plane;
-    r.n3 = s->d.n3;
-    r.f0 = s->put_f0;
-    r.nf = s->put_f1 - s->put_f0;
-    r.depth = s->put_deep ? 2 : 1;
-    r.sides = sides;
-    w.recv = 1;
-    blocks = pft_halo_wait_blocks(4L * r.nf * s->plane, local_staged, s->gpu_ranks, ws == s->bnd);
-  }
-  if (s->wait_streamops) {
-    // A/B (PFT_WAIT_STREAMOPS=1): the runtime's stream waits, then a separate receive launch
-    for (int side = 0; side < 2; ++side)
-      if (s->peer[side].on) HIPCHK(hipStreamWaitValue64(ws, s->sig + side, seq, hipStreamWaitValueGte, ~0ULL));
-    if (sides) halo_recv_kernel<<<blocks, 256, 0, ws>>>(w.r);
-  } else {
-    halo_wait_kernel<<<blocks, 256, 0, ws>>>(w);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// Workgroups of one halo_wait_kernel launch with a staged receive of n doubles.  Every block spins
-// on the flags before it copies, so the count bounds the CUs a wait can hold while the neighbour
-// whose launch raises the flag may need them:
-//  - a staged neighbour on this same GPU (PFT_IPC_STAGED between processes), or any other rank
-//    sharing this GPU (gpu_ranks > 1: N ranks per GPU, whose neighbours may sit on another GPU and
-//    depend on a rank of ours): 32 blocks.  A thousand spinning blocks would leave no CU for a pair
-//    kernel's workgroup (the whole register file of a CU) of the rank that raises the flag, which
-//    then waits out PFT_IPC_TIMEOUT -- or, across two GPUs, closes a wait cycle through both;
-//  - in the boundary pipeline (the wait beside an interior launch that does not wait for it): 128
-//    blocks of 4 waves, 16 CUs' worth; the 20 MB of the receive still take ~10 us;
-//  - otherwise (this rank alone on its GPU, waiting on the compute stream): up to 1024.
-int pft_halo_wait_blocks(long n, int local_staged, int gpu_ranks, int on_boundary_stream)
-{
-  int blocks = (int)std::min<long>(1024, std::max<long>(1, (n + 255) / 256));
-  if (local_staged || gpu_ranks > 1) blocks = std::min(blocks, 32);
-  if (on_boundary_stream) blocks = std::min(blocks, 128);
-  return blocks;
-}
-
-int pft_slab_set_gpu_ranks(pft_slab* s, int n)
-{
-  if (!s || n < 1) return -2;
-  s->gpu_ranks = n;
-  return 0;
-}
 
 int pft_flat_alloc(double** p, size_t n)
 {

@@ -3,8 +3,10 @@
 // helpers that cross files, and the dispatch from the runtime (stage, calc_mode, gl_static) to the
 // kernels' template arguments.  The translation units over the C ABI of include/pft_hip.h:
 //   pft_kernels.hip  the step kernels (merson_stage, merson_fused, merson_pair), the slab object's
-//                    API, the pft_hip_* shim, the halo exchange, IC
-//   pft_reduce.hip   diagnostics, exact means, formula diagnostics and histograms (f5, f6, f12, f13)
+//                    API, the pft_hip_* shim
+//   pft_halo.hip     the halo exchange (ipc transport, copy engines, boundary stream, trigger kernel)
+//   pft_ic.hip       the initial condition on the device (f1)
+//   pft_reduce.hip  diagnostics, exact means, formula diagnostics and histograms (f5, f6, f12, f13)
 //   pft_snap.hip     snapshots (f7), region snapshots (f11)
 // No device code crosses files: nothing is device-linked.  Every .hip includes this header first.
 #pragma once
@@ -254,9 +256,10 @@ struct pft_slab {
 // and the K's -- the default for even n1); 1 was the retired LDS-tiled aux-array kernel
 enum { KCACHE = 0, KFUSED = 2 };
 
-// host helpers that cross files (pft_kernels.hip), each commented at its definition
-PFT_LOCAL int slab_poisoned(pft_slab* s, const char* what);
+// host helpers that cross files, each commented at its definition
+PFT_LOCAL int slab_poisoned(pft_slab* s, const char* what);              // pft_kernels.hip
 PFT_LOCAL int slab_wait(pft_slab* s, hipEvent_t ev, const char* what);
+PFT_LOCAL void slab_trigger(pft_slab* s);                                // pft_halo.hip
 
 // The runtime (stage, calc_mode, flag) to template arguments: f is a generic lambda, called with the
 // value as a std::integral_constant, so each call site names its kernel once and the compiler

@@ -2,7 +2,7 @@
  * pft_tanh.h -- tanh() exactly as the host's C library computes it, for the device initial
  * condition (f1: the glass walls and beads of PrecalculateData, equation.c:459-530, and the default
  * Params' gl formula).  Compiled both as C (gcc, the CPU check tests/test_tanh.py) and as HIP
- * device code (pft_kernels.hip); always without contraction (-ffp-contract=off).
+ * device code (pft_ic.hip); always without contraction (-ffp-contract=off).
  *
  * glibc 2.35's x86_64 tanh is the generic sysdeps/ieee754/dbl-64 code: fdlibm's s_tanh.c on top of
  * fdlibm's s_expm1.c, whose polynomial glibc evaluates in the split form
